@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the upscale hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -9,8 +9,10 @@ One "step" = one batch of --frames-per-step synthetic 2048x1024 RGB frames pushe
 column FFT / zero-pad / iFFT -> C2R rows -> sharpen) on each GPU, inputs resident in HBM (a ring of --ring distinct
 frames per GPU).  The default step is 1024 frames, i.e. the reference's `-n 1000` run (BASELINE config 2) per step.
 Frames are independent, so N GPUs = N independent shards, no data-path collective ("weak" scaling: per-GPU work
-fixed).  The K-step timed region (barrier + synchronize on both sides, MAX over ranks) is repeated --repeats times
-and the MEDIAN region gives `value`.  Rank 0 prints ONE JSON line.
+fixed).  The K-step timed region (barrier + synchronize on both sides, MAX over ranks) runs once -- K timed steps in all
+-- unless --repeats R asks for R such regions, whose MEDIAN then gives `value`; `ms_per_step` is that region's time over K.
+Rank 0 prints ONE JSON line.  --dump-outputs DIR writes what the last timed step computed (the output frames a caller would
+download) as DIR/<name>.npy, see dump_outputs().
 
 At N = 1 the same invocation also times, briefly, the other single-GPU BASELINE configurations and the reference's own
 `-n 1000` figure (`others`: config3 = -p 2 with the fused uint8 load, config4 = 1920x1080, execute_n1000 =
@@ -46,7 +48,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=25)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=5, help="the K-step timed region is run this many times; the median is reported")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="the K-step timed region is run this many times (K x R timed steps in all); the median region is reported")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the output frames of the last step as DIR/<name>.npy (float32, float64 for -p 1; "
+                         "at most 64 MB in all: a fixed, seeded sample of every frame's values where the frames are larger)")
     ap.add_argument("--frames-per-step", type=int, default=1024)
     ap.add_argument("--preset", choices=sorted(PRESETS), default=None, help="a BASELINE.json configuration (default: config2 = headline)")
     ap.add_argument("--ring", type=int, default=8,
@@ -95,7 +101,33 @@ def parse_args():
         a.ring = a.frames_per_step * int(os.environ.get("WORLD_SIZE", "1"))       # any rank may be handed any frame of the step
     if a.job and a.ring < a.frames_per_step:
         ap.error("--job needs --ring >= --frames-per-step (every frame of a step resident and distinct)")
+    if a.dump_outputs and a.png:
+        ap.error("--dump-outputs writes pixel arrays; --png returns encoded files")
     return a
+
+
+DUMP_BYTES = 64 << 20          # --dump-outputs: at most this many bytes of arrays in all
+DUMP_SEED = 1234               # ... and the seed of the sample of values taken from frames larger than that
+
+
+def dump_outputs(out_dir, frames, size, prefix=""):
+    """--dump-outputs: frames = [(name, function returning the array)], each array of `size` values as the caller receives it (planar [3][uH][uW] of the plan's precision, or 8-bit
+    RGB [uH][uW][3]).  Each becomes out_dir/<prefix><name>.npy in float32 (float64 for -p 1 frames).  Frames whose values do not
+    fit DUMP_BYTES together are sampled: the same seeded, sorted flat positions in every frame (flat index order of the array as
+    received); the JSON line records the count.  Returns the line's `dump_outputs` entry."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    if not frames:
+        return {"dir": out_dir, "arrays": 0}
+    n = min(size, DUMP_BYTES // (8 * len(frames)))       # (8 bytes a value: float64 frames fit too)
+    idx = None if n == size else np.sort(np.random.default_rng(DUMP_SEED).choice(size, n, replace=False))
+    for name, get in frames:
+        a = get()
+        assert a.size == size
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32).reshape(-1)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a if idx is None else a[idx])
+    return {"dir": out_dir, "arrays": len(frames), "values_per_array": int(n), "values_per_frame": int(size),
+            "sample": None if idx is None else "np.random.default_rng(%d).choice(%d, %d, replace=False), sorted" % (DUMP_SEED, size, n)}
 
 
 def config_key(args):
@@ -450,9 +482,9 @@ def rccl_selfcheck(dev):
     try:
         r = subprocess.run([sys.executable, "-c", RCCL_SELFCHECK, str(dev)], capture_output=True, text=True, timeout=180)
         for l in r.stdout.splitlines():
-            if l.startswith("RCCL "):
+            if l.startswith("RCCL {"):                  # (RCCL's own banner lines start with "RCCL " too)
                 return json.loads(l[5:])
-        return {"ok": False, "error": "exit code %d: %s" % (r.returncode, r.stderr[-400:])}
+        return {"ok": False, "error": "exit code %d: %s | %s" % (r.returncode, r.stdout[-400:], r.stderr[-400:])}
     except Exception as e:                                   # reported, never hidden: tests/test_gpu_bench.py asserts ok
         return {"ok": False, "error": "%s: %s" % (type(e).__name__, e)}
 
@@ -592,10 +624,17 @@ def main():
         up.execute_ring(args.frames_per_step, slot)
         slot = (slot + args.frames_per_step) % args.ring
 
+    kms = [0.0] * len(up.kernel_names)
+    if not args.host_streamed and not args.queue:
+        # HIP events before/after every kernel launch of every --event-stride-th frame, on the stream that runs it: one step of its
+        # own, untimed (the events are not part of the path the timed steps measure)
+        _, kms = up.execute_ring_timed(args.frames_per_step, slot, args.event_stride)   # blocks until the batch is done
+        slot = (slot + args.frames_per_step) % args.ring
+
     # ---- timed regions: EXACTLY --steps steps each, barrier + synchronize on both sides, MAX over ranks; median of --repeats
     power = PowerSampler(v.device_pci_bus_id(dev)).start() if rank == 0 else None
     region_s, region_dev_ms, region_own_s = [], [], []
-    kms = [0.0] * len(up.kernel_names)
+    last_slots = []                            # output slots the step that ran last wrote, in order
     for rep in range(max(1, args.repeats)):
         barrier()
         t0 = time.perf_counter()
@@ -609,13 +648,8 @@ def main():
             if args.queue:
                 dev_ms += queue_step()
                 continue
-            if rep == 0:
-                # HIP events before/after every kernel launch of every --event-stride-th frame, on the stream that runs it
-                ms, km = up.execute_ring_timed(args.frames_per_step, slot, args.event_stride)   # blocks until the batch is done
-                kms = [a + b / args.steps for a, b in zip(kms, km)]
-            else:
-                ms = up.execute_ring(args.frames_per_step, slot)
-            dev_ms += ms
+            dev_ms += up.execute_ring(args.frames_per_step, slot)
+            last_slots = list(dict.fromkeys((slot + k) % args.ring for k in range(args.frames_per_step)))
             slot = (slot + args.frames_per_step) % args.ring
         t_own = time.perf_counter() - t0      # this rank's own work, before the closing barrier: a sagging rank shows here
         barrier()
@@ -628,6 +662,17 @@ def main():
         region_own_s.append(t_own)
         region_dev_ms.append(dev_ms)
     power_stats = power.stop() if power is not None else None
+    dumped = None
+    if args.dump_outputs:
+        # what the last timed step handed its caller, before anything else runs on the plan (profile_kernels reuses the slots)
+        if args.host_streamed:
+            last_slots = list(dict.fromkeys(k % args.ring for k in range(args.frames_per_step)))
+            frames = [("out_slot%d" % s, lambda s=s: pins[1].array[s]) for s in last_slots]
+        else:
+            if args.queue:
+                last_slots = [g for (a, b) in claimed for g in range(a, b)]
+            frames = [("out_slot%d" % s, lambda s=s: up.download_rgb8(s) if up.u8_store else up.download_planar(s)) for s in last_slots]
+        dumped = dump_outputs(args.dump_outputs, frames, 3 * up.out_width * up.out_height, "rank%d_" % rank if world > 1 else "")
     order = sorted(range(len(region_s)), key=lambda i: region_s[i])
     med = order[len(order) // 2]
     dt = region_s[med]
@@ -678,8 +723,9 @@ def main():
                          else "frame f*world + rank (VkResample.cpp:1622-1629)"}
     line = None
     if rank == 0:
-        # kms: average kernel durations inside the first timed region (consecutive frames overlap on --streams lanes, so a
-        # kernel's duration there includes the time it shares the GPU with the other lanes' kernels);
+        # kms: average kernel durations in the untimed step of per-kernel events before the timed regions, launched as the timed
+        # steps launch them (consecutive frames overlap on --streams lanes, so a kernel's duration there includes the time it shares
+        # the GPU with the other lanes' kernels);
         # iso: the same kernels launched strictly one after the other right after the timed regions, HIP events on the
         # launching stream, net of the cost of an empty event pair (= what rocprofv3 --kernel-trace --stats reports)
         iso = up.profile_kernels(args.profile_iters)
@@ -760,6 +806,8 @@ def main():
             # at the power limit this is the number a kernel change has to move: joules per frame
             power_stats["energy_mj_per_frame"] = power_stats["socket_power_w_median"] * wall_frame_ms       # (one GPU works on a frame)
         line["power"] = power_stats
+        if dumped is not None:
+            line["dump_outputs"] = dumped
         if args.host_streamed:
             pcie = 3.0 * (args.width * args.height + up.out_width * up.out_height)
             if args.png:

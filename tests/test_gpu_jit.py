@@ -3,7 +3,6 @@ C2R+sharpen kernels instantiated through hipRTC at plan time.  Parity against th
 test_gpu_parity.test_full_size_vs_oracle) and against the size-generic kernels on the same frame, for sizes that
 exercise every plan family: three-stage mixed-radix rows/columns, power-of-two rows/columns, the 16*16*R fused plans,
 the N-stage fused plans (four stages, several butterflies per thread), the stand-alone C2R of the pre-sharpen tap."""
-import os
 
 import numpy as np
 import pytest
@@ -36,13 +35,6 @@ JIT_SIZES = [
 @pytest.mark.parametrize("W,H", JIT_SIZES)
 @pytest.mark.parametrize("precision,flags", [(0, 0), (0, 2), (2, 2)])
 def test_specialised_plan_vs_oracle(W, H, precision, flags):
-    big = os.environ.get("FFTUP_BIG_TESTS", "0") != "0"
-    if W > 3000 and (precision, flags) != (0, 0) and not big:
-        pytest.skip("8K outputs: fp32 only unless FFTUP_BIG_TESTS=1 (the oracle takes 10 s per case)")
-    if (precision, flags) == (2, 2) and JIT_SIZES.index((W, H)) % 2 and not big:
-        pytest.skip("-p 2 on every other size of the list unless FFTUP_BIG_TESTS=1 (time limit of the driver's GPU run)")
-    if (precision, flags) == (0, 2) and (W, H) not in ((640, 480), (1000, 1000), (1024, 768), (896, 504), (2000, 1250)) and not big:
-        pytest.skip("fp32 with the fused uint8 load (the planar row kernel with another loader): one size per row-kernel family unless FFTUP_BIG_TESTS=1")
     with _up(W, H, 2.0, precision, 0.2, 0, flags) as up:
         assert up.tuned and up.specialised_at_plan_time, "plan fell back to the size-generic kernels"
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, 2.0, precision, "N", flags=flags, seed=W + H)
@@ -79,7 +71,7 @@ U_CASES = [
     (640, 480, 2.5),     # first radix 10, D = 5
     (1280, 2160, 1.5),   # uH = 3240: k_col_pad with two columns per workgroup
     (640, 3000, 3.0),    # k_col_u with two columns per workgroup
-    (5120, 2880, 1.5),   # 5K -> 8K: the widest input (7680 output columns), uH = 4320 (FFTUP_BIG_TESTS=1)
+    (5120, 2880, 1.5),   # 5K -> 8K: the widest input (7680 output columns), uH = 4320
     # quarter-integer factors (round 5): the factor is D / (2 DD) with DD = 2 -- the fused kernel's first radix makes R0 DD / D whole
     (1280, 720, 1.25),   # 5/4: fused 10*10*16, NI = 4 of 10 first-stage inputs non-zero
     (1024, 512, 1.25),   # row pow2/8, fused 10*8*16
@@ -118,12 +110,6 @@ U_CASES = [
 @pytest.mark.parametrize("W,H,u", U_CASES)
 @pytest.mark.parametrize("precision,flags", [(0, 0), (2, 2)])
 def test_specialised_integer_factor_vs_oracle(W, H, u, precision, flags):
-    if os.environ.get("FFTUP_BIG_TESTS", "0") == "0" and (W * H * u * u > 30e6 or (W * H * u * u > 12e6 and precision == 0)):
-        pytest.skip("outputs above 12 Mpixel: -p 2 with the fused u8 load only, above 30 Mpixel nothing, unless FFTUP_BIG_TESTS=1 (oracle time)")
-    if os.environ.get("FFTUP_BIG_TESTS", "0") == "0" and W * H * u * u <= 12e6 and U_CASES.index((W, H, u)) % 2 == (1 if precision == 2 else 0) \
-            and (W, H, u) not in ((1920, 1080, 1.5), (1280, 720, 3.0), (1920, 1080, float(np.float32(4.0 / 3.0)))):
-        pytest.skip("one precision per case of the list (alternating; both for three everyday ones) unless FFTUP_BIG_TESTS=1: the driver's whole GPU "
-                    "run has a time limit (VERDICT r5 #1); tools/gpu_final_checks.sh runs them all")
     with _up(W, H, u, precision, 0.2, 0, flags) as up:
         assert up.tuned and up.specialised_at_plan_time, "plan fell back to the size-generic kernels"
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, precision, "N", flags=flags, seed=W + H)

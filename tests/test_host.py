@@ -466,3 +466,29 @@ def test_jit_check_takes_any_float_factor():
             m = re.search(r"fused ([\d*]+|pow2/8)", buf.value.decode())
             assert m, buf.value
     assert seen > 300
+
+
+def test_bench_dump_outputs_sample_is_fixed_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs on the host side: frames that fit are written whole (float32; float64 stays float64); frames that do
+    not fit the byte budget together are sampled at the same seeded positions in every frame, and the files stay within it"""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.default_rng(3)
+    half = [rng.random((3, 8, 10)).astype(np.float16) for _ in range(3)]
+    info = bench.dump_outputs(str(tmp_path / "a"), [("f%d" % i, lambda a=a: a) for i, a in enumerate(half)], 240)
+    assert info["arrays"] == 3 and info["values_per_array"] == 240 and info["sample"] is None
+    for i, a in enumerate(half):
+        got = np.load(tmp_path / "a" / ("f%d.npy" % i))
+        assert got.dtype == np.float32 and np.array_equal(got, a.astype(np.float32).reshape(-1))
+    monkeypatch.setattr(bench, "DUMP_BYTES", 2000)
+    big = [rng.random(1000) for _ in range(2)]
+    runs = []
+    for d in ("b", "c"):
+        info = bench.dump_outputs(str(tmp_path / d), [("g%d" % i, lambda a=a: a) for i, a in enumerate(big)], 1000)
+        assert info["values_per_array"] == 125 and info["sample"]
+        runs.append([np.load(tmp_path / d / ("g%d.npy" % i)) for i in range(2)])
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= 2000 + 2 * 128     # (+ .npy headers)
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(1000, 125, replace=False))
+    for i in range(2):
+        assert runs[0][i].dtype == np.float64 and np.array_equal(runs[0][i], runs[1][i]) and np.array_equal(runs[0][i], big[i][idx])
