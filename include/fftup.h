@@ -66,10 +66,25 @@ enum {
                                         fftup_info.u8_store says which it is                                               */
     FFTUP_FLAG_SEQUENTIAL_EXECUTE = 64u, /* accepted and ignored: ordered iterations are what fftup_execute does (0.6 and earlier
                                         needed this flag for it)                                                               */
-    FFTUP_FLAG_OVERLAP_ITERATIONS = 128u /* EXTENSION, not the reference's semantics: the n_iter identical iterations of one
+    FFTUP_FLAG_OVERLAP_ITERATIONS = 128u, /* EXTENSION, not the reference's semantics: the n_iter identical iterations of one
                                         fftup_execute call alternate on the plan's streams and overlap like the distinct frames
                                         of fftup_execute_ring (a throughput figure; same bits).  A plan without a ring is then
                                         laid out for overlapping frames (one strip of the last kernel per compute unit)         */
+    FFTUP_FLAG_DCT = 256u            /* EXTENSION (0.7.0; older libraries ignore the bit): DCT upscale instead of the FFT's -- the
+                                        image is not treated as periodic, so a frame whose opposite borders differ gets no ringing
+                                        there.  Per axis, separable, input x[n] (n < N), output y[m] (m < M = (uint32_t)(u N), the
+                                        FFT path's size rule):  X[k] = sum_n x[n] cos(pi k (2n+1) / 2N)  (DCT-II), then
+                                        y[m] = X[0]/N + (2/N) sum_{k=1}^{N-1} X[k] cos(pi k (2m+1) / 2M)  (DCT-III of the
+                                        zero-padded coefficients).  Samples sit at pixel CENTRES: output pixel m lies at input
+                                        position (m + 1/2) N / M - 1/2, where the FFT path puts pixel 0 on pixel 0.  Constants
+                                        stay constant, -u 1 reproduces the input, no Nyquist special case (the FFT path's quirks
+                                        B1 / B2 do not apply).  The pre-sharpen image R keeps the FFT path's convention upsq R = y
+                                        and the sharpen pass is the FFT path's, unchanged (its wrap at the right edge, quirk B5,
+                                        included).  Four launches, size-generic kernels: the plan-time, ahead-of-time and fused
+                                        kernels and FFTUP_FLAG_FUSE_U8_STORE do not apply (fftup_info.tuned = u8_store = 0).
+                                        Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), u*W <= 8192 and columns
+                                        whose transforms fit the compute unit's local memory (no four-step DCT):
+                                        FFTUP_E_UNSUPPORTED_SIZE otherwise                                                     */
 };
 
 /* Replaces VkResampleConfiguration (VR:45-59) + the part of VkFFTConfiguration (VF:22-94) that
@@ -130,7 +145,8 @@ FFTUP_API int fftup_device_pci_bus_id(int device, char* buf, size_t buflen);
  * (VR:1437-1448, 1506-1509, 1562, 1617).  Every even 2,3,5,7-smooth width and height up to 65536 whose upscaled sizes are
  * even and smooth is a valid plan, as in the reference: upscaled widths beyond 8192 (4096 for -p 1) take the reference's
  * non-R2C path (VR:1424); rows and columns too long for the compute unit's local memory run as two-launch "four-step"
- * transforms through device memory (the reference's multi-upload plans, VF:4773-4992).  fftup_plan_describe says which. */
+ * transforms through device memory (the reference's multi-upload plans, VF:4773-4992).  fftup_plan_describe says which.
+ * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag). */
 FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);

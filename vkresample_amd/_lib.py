@@ -16,6 +16,7 @@ FLAG_TUNE_PLAN = 16
 FLAG_FUSE_U8_STORE = 32
 FLAG_SEQUENTIAL_EXECUTE = 64      # (accepted and ignored: ordered iterations are the default)
 FLAG_OVERLAP_ITERATIONS = 128
+FLAG_DCT = 256                    # DCT-II -> zero-pad -> DCT-III instead of the periodic FFT (library 0.7.0 on)
 
 # every symbol include/fftup.h declares
 EXPORTS = [

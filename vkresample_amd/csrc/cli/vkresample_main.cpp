@@ -15,6 +15,7 @@
 //   -tune         FFTUP_FLAG_TUNE_PLAN: time the alternatives for a size specialised at plan time, keep the fastest (wisdom file)
 //   -overlap      FFTUP_FLAG_OVERLAP_ITERATIONS: the -n iterations alternate on the plan's streams ("Time:" = throughput; the
 //                 default keeps them in order like the reference's barriers, VR:1217, vkFFT.h:7678)
+//   -dct          FFTUP_FLAG_DCT: DCT-II -> zero-pad -> DCT-III instead of the periodic FFT (no wrap-around ringing at the borders)
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -337,6 +338,7 @@ int main(int argc, char* argv[])
         printf("	-stagetimes: batched mode: every thread reports its host time by stage (decode, submit, wait, encode)\n");
         printf("	-tune: sizes whose kernels are specialised at plan time: measure the alternatives once, remember the fastest\n");
         printf("	-overlap: the -n iterations overlap on several streams: 'Time:' becomes a throughput figure, not the original's serial one\n");
+        printf("	-dct: DCT upscale instead of FFT: the image is not treated as periodic, no ringing at the borders (-p 0 and -p 2)\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -378,6 +380,7 @@ int main(int argc, char* argv[])
     if (findFlag(B, E, "-wrapu8")) config.flags |= FFTUP_FLAG_U8_WRAP;
     if (findFlag(B, E, "-tune")) config.flags |= FFTUP_FLAG_TUNE_PLAN;
     if (findFlag(B, E, "-overlap")) config.flags |= FFTUP_FLAG_OVERLAP_ITERATIONS;
+    if (findFlag(B, E, "-dct")) config.flags |= FFTUP_FLAG_DCT;
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");
 

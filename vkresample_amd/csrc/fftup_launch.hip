@@ -16,6 +16,7 @@
 #include "kernels_pow2.hpp"
 #include "kernels_mixed.hpp"
 #include "kernels_dswap.hpp"
+#include "kernels_dct.hpp"
 
 using namespace fftup;
 
@@ -102,6 +103,17 @@ int kernels_set_attributes(fftup_plan* P)
     const uint32_t H = P->H, uW = P->uW;
 #define PLAN_TRY(expr) HIP_TRY(expr)
 #define SET_LDS(kern, bytes) PLAN_TRY(hipFuncSetAttribute((const void*)(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(bytes)))
+        if (P->dct) {                                        // (the DCT plan's kernels only: kernels_dct.hpp)
+            if (P->half) { SET_LDS(k_dct_row<IN_F16>, P->ldsRowF); SET_LDS(k_dct_row<IN_U8_F16>, P->ldsRowF); SET_LDS(k_idct_row<true>, P->ldsRowI); }
+            else { SET_LDS(k_dct_row<IN_F32>, P->ldsRowF); SET_LDS(k_dct_row<IN_U8_F32>, P->ldsRowF); SET_LDS(k_idct_row<false>, P->ldsRowI); }
+            switch (P->TK) {
+            case 8: SET_LDS(k_dct_col<8>, P->ldsCol); break;
+            case 4: SET_LDS(k_dct_col<4>, P->ldsCol); break;
+            case 2: SET_LDS(k_dct_col<2>, P->ldsCol); break;
+            default: SET_LDS(k_dct_col<1>, P->ldsCol); break;
+            }
+            return FFTUP_OK;
+        }
         const bool generic = !P->tuned && !P->mixed;
         // (same predicate as launch_frame: a plan-time plan without a row factorization runs the size-generic row kernel)
         const bool generic_rows = generic || (P->mixed == 3 && P->jit->choice.row_kind == 2);
@@ -348,6 +360,65 @@ static void launch_sharpen_fast(fftup_plan* P, uint32_t out_slot)
     else hipLaunchKernelGGL((k_sharpen_t<false, 4>), grid, block, 0, P->lanes[P->cur].stream, p);
 }
 
+// the sharpen pass of an unfused fp32 / fp16 plan on lane P->cur: R -> output slot
+static void launch_sharpen(fftup_plan* P, uint32_t out_slot)
+{
+    if (fast_sharpen_ok(P)) { launch_sharpen_fast(P, out_slot); return; }
+    SharpenParams p{};
+    p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    dim3 grid((P->uW + 1023) / 1024, P->uH, 3), block(256);      // (four pixels per thread; a width of 2 gave an empty grid until round 5)
+    if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, P->lanes[P->cur].stream, p);
+    else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, P->lanes[P->cur].stream, p);
+}
+
+// FFTUP_FLAG_DCT: DCT-II rows -> DCT-II columns, zero-pad, DCT-III columns -> DCT-III rows -> sharpen (kernels_dct.hpp)
+static int launch_frame_dct(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+{
+    hipStream_t st = P->lanes[P->cur].stream;
+    const int kind = P->in_kind[in_slot];
+    if (which < 0 || which == 0) {
+        DctRowParams p{};
+        p.S1 = (float*)P->lanes[P->cur].S1; p.tw = P->twW; p.rot = P->rotW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        const dim3 grid(P->H / 2, 3), block(P->thrW);
+        if (kind == 2) {
+            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            if (P->half) hipLaunchKernelGGL(k_dct_row<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_dct_row<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
+        } else {
+            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            if (P->half) hipLaunchKernelGGL(k_dct_row<IN_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_dct_row<IN_F32>, grid, block, P->ldsRowF, st, p);
+        }
+    }
+    if (which < 0 || which == 1) {
+        DctColParams p{};
+        p.S1 = (const float*)P->lanes[P->cur].S1; p.S2 = (float*)P->lanes[P->cur].S2;
+        p.twH = P->twH; p.twUH = P->twUH; p.rotH = P->rotH; p.rotUH = P->rotUH; p.planH = P->planH; p.planUH = P->planUH;
+        p.W = (int)P->W; p.H = (int)P->H; p.uH = (int)P->uH; p.inv_norm = (float)(1.0 / (double)P->H);
+        const dim3 grid((P->W / 2 + P->TK - 1) / P->TK, 3), block(P->thrCol);
+        switch (P->TK) {
+        case 8: hipLaunchKernelGGL(k_dct_col<8>, grid, block, P->ldsCol, st, p); break;
+        case 4: hipLaunchKernelGGL(k_dct_col<4>, grid, block, P->ldsCol, st, p); break;
+        case 2: hipLaunchKernelGGL(k_dct_col<2>, grid, block, P->ldsCol, st, p); break;
+        default: hipLaunchKernelGGL(k_dct_col<1>, grid, block, P->ldsCol, st, p); break;
+        }
+    }
+    if (which < 0 || which == 2) {
+        IdctRowParams p{};
+        p.S2 = (const float*)P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.rot = P->rotUW; p.plan = P->planUW;
+        p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH;
+        p.inv_norm = (float)(1.0 / ((double)P->W * (double)P->upsq));
+        const dim3 grid(P->uH / 2, 3), block(P->thrUW);
+        if (P->half) hipLaunchKernelGGL(k_idct_row<true>, grid, block, P->ldsRowI, st, p);
+        else hipLaunchKernelGGL(k_idct_row<false>, grid, block, P->ldsRowI, st, p);
+        P->R_valid = true;
+    }
+    if (which < 0 || which == 3) launch_sharpen(P, out_slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FFTUP_OK;
+}
+
 // -p 1: the size-generic kernels instantiated on double2 + the double sharpen
 static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
@@ -541,6 +612,7 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
     if (kind == 0 && which != 22) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (22, the pre-sharpen tap, reads spectra only)
     if (P->cplx) return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
     if (P->dbl) return launch_frame_f64(P, in_slot, out_slot, which);
+    if (P->dct) return launch_frame_dct(P, in_slot, out_slot, which);
     if (P->tuned) {
         launch_frame_tuned(P, in_slot, out_slot, which);
         if ((which < 0 || which == 3) && !P->fused) launch_sharpen_fast(P, out_slot);
@@ -630,14 +702,8 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
     }
     if (P->fused) {
         // sharpen is part of launch 2
-    } else if ((which < 0 || which == 3) && fast_sharpen_ok(P)) {
-        launch_sharpen_fast(P, out_slot);
     } else if (which < 0 || which == 3) {
-        SharpenParams p{};
-        p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
-        dim3 grid((P->uW + 1023) / 1024, P->uH, 3), block(256);      // (four pixels per thread; a width of 2 gave an empty grid until round 5)
-        if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, P->lanes[P->cur].stream, p);
-        else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, P->lanes[P->cur].stream, p);
+        launch_sharpen(P, out_slot);
     }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = jerr;

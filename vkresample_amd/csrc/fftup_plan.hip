@@ -119,6 +119,20 @@ static int make_twiddles(fftup_plan* P, float2** dptr, uint32_t n)
     return FFTUP_OK;
 }
 
+// DCT plans: the pre- and post-rotations exp(i pi k / 2n), k < n, in double, rounded once to fp32 (as make_twiddles)
+static int make_rotations(fftup_plan* P, float2** dptr, uint32_t n)
+{
+    std::vector<float2> h(n);
+    for (uint32_t k = 0; k < n; k++) {
+        const double a = M_PI * (double)k / (2.0 * (double)n);
+        h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
+    return FFTUP_OK;
+}
+
 // the sharpen constants reach the reference's shader as "%f" text (VkResample.cpp:893-901, 920)
 static float const_via_percent_f(double v, bool half)
 {
@@ -333,6 +347,10 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     // R2C rule of the reference: uW <= maxComputeSharedMemorySize/8 with 64 KB (VkResample.cpp:1424; complexSizeCalc = 16
     // for -p 1, VkResample.cpp:1334-1336, halves the limit); beyond it the full complex path runs
     const bool cplx = uW > (cfg->precision == 1 ? 4096u : 8192u);
+    // DCT plans (FFTUP_FLAG_DCT): fp32 / fp16 storage, rows in one LDS launch (no non-R2C-like path for uW beyond 8192)
+    const bool dct = (cfg->flags & FFTUP_FLAG_DCT) != 0;
+    if (dct && cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_DCT plans exist for -p 0 and -p 2");
+    if (dct && uW > 8192u) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need an upscaled width of at most 8192");
     // (checked here, before any device access: gfx950 has 160 KB of LDS per workgroup.)  Non-R2C rows whose two Stockham
     // buffers do not fit run in ONE buffer (fft_lds_inplace: up to 16 384 complex fp32 points, 1024 threads, every stage
     // N/R <= (16/R) * 1024: radix 7 up to 14336 points, 3 and 5 up to 15360); the reference switches to multi-upload plans there (vkFFT.h:4773-4992)
@@ -364,6 +382,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     P->half = cfg->precision == 2;
     P->dbl = cfg->precision == 1;
     P->cplx = cplx;
+    P->dct = dct;
     P->ncols = cplx ? (int)W : (int)(W / 2 + 1);
     P->esz = P->dbl ? 8 : (P->half ? 2 : 4);
     P->csz = P->dbl ? 16 : 8;
@@ -407,7 +426,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         // (experiment aot=0: the sizes with ahead-of-time kernels go through the plan-time compiler as well)
         const char* const aot_e = fftup_jit::experiment("aot");
         const bool aot = !(aot_e && atoi(aot_e) == 0);
-        P->tuned = aot && !P->dbl && !cplx && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
+        P->tuned = aot && !P->dbl && !cplx && !dct && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
                    (W == 512 || W == 1024 || W == 2048) && (H == 256 || H == 512 || H == 1024);
         P->TK = 0;
         if (P->tuned) {
@@ -417,7 +436,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             // u = 2 with the symmetric guard: the polyphase column kernel (k_col_poly: forward, phase, length-H inverse in ONE buffer of
             // H TK points, odd rows out; the C2R kernel takes the even rows from S1) where its stages run in place
             const char* const poly_e = fftup_jit::experiment("generic_poly");
-            if (!cplx && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
+            if (!cplx && !dct && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
                 for (int tk : {8, 4, 2, 1}) {
                     const size_t need = P->csz * (size_t)lpad_size((int)H * tk);
                     const int thr = inplace_threads(P->planH, tk, COL_INPLACE_PT, kernels_generic_max_threads(P->dbl));
@@ -441,6 +460,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                 if (need <= lds_max) { P->TK = tk; P->ldsCol = need; break; }
             }
         }
+        if (!P->TK && dct) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT: the columns do not fit the LDS (no four-step DCT)"); goto bad; }
         if (!P->TK) {
             // not even one column fits: tiles of one column, both column transforms in four steps through HBM (k_row4_a / k_row4_b)
             P->TK = 1; P->ldsCol = 0;
@@ -455,13 +475,13 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                 f.thrB = std::min(tmax, std::max(64, round_up(f.n2 * f.tkb / 8, 64)));
             }
         }
-        if (aot && !P->dbl && !cplx && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
+        if (aot && !P->dbl && !cplx && !dct && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
             P->mixed = kernels_aot_mixed_plan(W, H);                    // 1920x1080, 1280x720
         }
         if (P->mixed) { P->TK = 4; P->ldsCol = sizeof(float2) * (size_t)H * 4; }             // k_col_m: one in-place buffer
         // any other size with an integer or half-integer upscale factor: kernels specialised for it now (the counterpart
         // of VkFFT generating its shaders at plan time)
-        if (!P->dbl && !cplx && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
+        if (!P->dbl && !cplx && !dct && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
             int DD = 1;
             const int D = jit_factor(cfg->upscale, W, H, uW, uH, P->zly, P->zry, &DD);
             if (D) {
@@ -525,6 +545,12 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         PLAN_RC(make_twiddles(P, &P->twUH, uH));
         for (fftup_plan::Four* f : {&P->fourF, &P->fourI, &P->colF, &P->colI})
             if (f->on) { PLAN_RC(make_twiddles(P, &f->tw1, (uint32_t)f->n1)); PLAN_RC(make_twiddles(P, &f->tw2, (uint32_t)f->n2)); }
+        if (dct) {
+            PLAN_RC(make_rotations(P, &P->rotW, W));
+            PLAN_RC(make_rotations(P, &P->rotH, H));
+            PLAN_RC(make_rotations(P, &P->rotUW, uW));
+            PLAN_RC(make_rotations(P, &P->rotUH, uH));
+        }
 
         const size_t esz = P->esz;
         P->in_plane_stride = (size_t)(W + 2) * H;                    // VkResample.cpp:1644
@@ -587,7 +613,9 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
 {
     if (!P || !buf || !buflen) return fail(FFTUP_E_INVALID_ARG, "null argument");
     std::string s;
-    if (P->mixed == 3) s = "specialised at plan time: " + fftup_jit::describe(P->jit->choice);
+    if (P->dct) s = "dct: size-generic DCT-II / zero-pad / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
+                    + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
+    else if (P->mixed == 3) s = "specialised at plan time: " + fftup_jit::describe(P->jit->choice);
     else if (P->tuned) s = "ahead-of-time power-of-two kernels (radix 8, 8 points per thread; fused C2R+sharpen " + std::string(P->fused ? "on" : "off") + ")"
                            + "; column kernel with digit-swap exchanges";
     else if (P->mixed) s = std::string("ahead-of-time mixed-radix kernels: ") + (P->mixed == 1 ? "row 15*8*16, col 9*10*12, fused 16*16*15" : "row 5*16*16, col 9*8*10, fused 16*16*10");
@@ -640,13 +668,20 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
         info->kernel_min_bytes[2] = P->fused ? S2 * halo + o : S2 + R;
         info->kernel_min_bytes[3] = P->fused ? 0.0 : R + o;
     }
+    if (P->dct) {
+        // real coefficients instead of half spectra: S1 = [3][H][W], S2 = [3][uH][W] fp32 ("DCT upscale mode")
+        const double D1 = C * W * H * 4.0, D2 = C * W * uH * 4.0;
+        info->alg_bytes_per_frame = in + 2 * D1 + 2 * D2 + 2 * R + o;
+        const double k[FFTUP_NUM_KERNELS] = {in + D1, D1 + D2, D2 + R, R + o};
+        for (int i = 0; i < FFTUP_NUM_KERNELS; i++) info->kernel_alg_bytes[i] = info->kernel_min_bytes[i] = k[i];
+    }
     info->device_bytes = P->device_bytes;
     info->abi_version = FFTUP_ABI_VERSION;
     info->u8_store = P->u8out ? 1 : 0;
     snprintf(info->device_name, sizeof info->device_name, "%s", device_label(P->prop));
-    snprintf(info->kernel_names[0], 64, P->cplx ? "row_c2c" : "row_r2c");
-    snprintf(info->kernel_names[1], 64, "col_fwd_pad_inv");
-    snprintf(info->kernel_names[2], 64, P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
+    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : P->cplx ? "row_c2c" : "row_r2c");
+    snprintf(info->kernel_names[1], 64, P->dct ? "dct_col_pad_idct" : "col_fwd_pad_inv");
+    snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
     return FFTUP_OK;
 }
@@ -670,7 +705,7 @@ const char* fftup_strerror(int code)
 }
 
 const char* fftup_last_error(void) { return g_last_error.c_str(); }
-const char* fftup_version(void) { return "fftup 0.5.0 (gfx950, ABI 2)"; }
+const char* fftup_version(void) { return "fftup 0.7.0 (gfx950, ABI 2)"; }
 
 }  // extern "C"
 

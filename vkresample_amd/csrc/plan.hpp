@@ -80,6 +80,7 @@ struct fftup_plan {
     fftup_jit::Module* jit = nullptr;
     int U = 2;                        // integer upscale factor of a polyphase plan (tuned / mixed): S1 + U-1 residue buffers
     bool cplx = false;                // non-R2C path (VR:1424 false): full complex transforms, uW beyond the R2C limit
+    bool dct = false;                 // FFTUP_FLAG_DCT: DCT-II -> zero-pad -> DCT-III (kernels_dct.hpp); S1 / S2 hold real [3][H][W] / [3][uH][W]
     bool poly = false;                         // size-generic u = 2 plan: polyphase column kernel (k_col_poly), the C2R kernel reads the even rows from S1
     bool inplaceC = false;                     // -p 1 R2C plans: the column kernel's two transforms in one LDS buffer (k_col<TK, double2, true>)
     bool inplaceF = false, inplaceI = false;   // ... whose forward / inverse rows are too long for two LDS buffers: fft_lds_inplace
@@ -124,6 +125,7 @@ struct fftup_plan {
     uint32_t* png_crc_shift = nullptr; // device table of k_png_crc (created with the first PNG slot)
     bool png_foreign_collector = false; // some thread has collected (fftup_wait_png) a ticket another thread submitted; under q_mu
     float2 *twW = nullptr, *twH = nullptr, *twUW = nullptr, *twUH = nullptr;
+    float2 *rotW = nullptr, *rotH = nullptr, *rotUW = nullptr, *rotUH = nullptr;    // DCT plans: exp(i pi k / 2n), k < n
     uint64_t device_bytes = 0;
     size_t r_bytes = 0;               // bytes of one pre-sharpen image
     uint64_t* d_sum = nullptr;        // fftup_output_checksum accumulator (created on first use)
