@@ -70,7 +70,7 @@ enum {
                                         fftup_execute call alternate on the plan's streams and overlap like the distinct frames
                                         of fftup_execute_ring (a throughput figure; same bits).  A plan without a ring is then
                                         laid out for overlapping frames (one strip of the last kernel per compute unit)         */
-    FFTUP_FLAG_DCT = 256u            /* EXTENSION (0.7.0; older libraries ignore the bit): DCT upscale instead of the FFT's -- the
+    FFTUP_FLAG_DCT = 256u,           /* EXTENSION (0.7.0; older libraries ignore the bit): DCT upscale instead of the FFT's -- the
                                         image is not treated as periodic, so a frame whose opposite borders differ gets no ringing
                                         there.  Per axis, separable, input x[n] (n < N), output y[m] (m < M = (uint32_t)(u N), the
                                         FFT path's size rule):  X[k] = sum_n x[n] cos(pi k (2n+1) / 2N)  (DCT-II), then
@@ -85,6 +85,24 @@ enum {
                                         Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), u*W <= 8192 and columns
                                         whose transforms fit the compute unit's local memory (no four-step DCT):
                                         FFTUP_E_UNSUPPORTED_SIZE otherwise                                                     */
+    FFTUP_FLAG_DOWNSCALE = 512u      /* EXTENSION: spectral DOWNSCALE, upscale in [0.125, 1) (FFTUP_E_INVALID_ARG otherwise; without
+                                        the flag a factor below 1 stays FFTUP_E_INVALID_ARG, so a library without this mode refuses
+                                        such a plan).  Output sizes by the usual rule uW = (uint32_t)(u W), uH = (uint32_t)(u H) in
+                                        fp32: even, at least 2 and below W, H (FFTUP_E_INVALID_ARG), 2,3,5,7-smooth
+                                        (FFTUP_E_UNSUPPORTED_SIZE).  FFT mode: per axis, separable, input x[n] (n < N), output length
+                                        M < N, h = M/2, X = DFT(x) unnormalised; the spectrum is cropped with its Nyquist bins folded,
+                                          Y[k] = X[k] (k < h),  Y[h] = X[h] + X[N-h],  Y[M-k] = X[N-k] (0 < k < h),
+                                        and R = (1/M) IDFT_M(Y) per axis; the amplitude-preserving image is y = R (uW uH) / (W H).
+                                        Per axis this is scipy.signal.resample: ideal band-limited decimation, output pixel m on
+                                        input position m N / M (pixel 0 on pixel 0, as the upscale path), constants stay constant,
+                                        content above the new Nyquist frequency vanishes (quirks B1-B3 do not apply).  The sharpen
+                                        pass is the upscale path's, unchanged (upsq = "%f"(u u), quirk B5).
+                                        With FFTUP_FLAG_DCT: the DCT mode's formula with the coefficients truncated instead of
+                                        zero-padded, y[m] = X[0]/N + (2/N) sum_{k=1}^{M-1} X[k] cos(pi k (2m+1) / 2M), R = y / upsq.
+                                        Four launches, size-generic kernels (fftup_info.tuned = u8_store = 0; FFTUP_FLAG_FUSE_U8_STORE,
+                                        _GENERIC_KERNELS, _UNFUSED_SHARPEN and _TUNE_PLAN are accepted and change nothing).
+                                        Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), W <= 8192 and columns whose
+                                        transforms fit the compute unit's local memory: FFTUP_E_UNSUPPORTED_SIZE otherwise       */
 };
 
 /* Replaces VkResampleConfiguration (VR:45-59) + the part of VkFFTConfiguration (VF:22-94) that
@@ -146,7 +164,7 @@ FFTUP_API int fftup_device_pci_bus_id(int device, char* buf, size_t buflen);
  * even and smooth is a valid plan, as in the reference: upscaled widths beyond 8192 (4096 for -p 1) take the reference's
  * non-R2C path (VR:1424); rows and columns too long for the compute unit's local memory run as two-launch "four-step"
  * transforms through device memory (the reference's multi-upload plans, VF:4773-4992).  fftup_plan_describe says which.
- * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag). */
+ * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag); FFTUP_FLAG_DOWNSCALE plans take factors below 1. */
 FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);

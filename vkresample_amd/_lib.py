@@ -17,6 +17,7 @@ FLAG_FUSE_U8_STORE = 32
 FLAG_SEQUENTIAL_EXECUTE = 64      # (accepted and ignored: ordered iterations are the default)
 FLAG_OVERLAP_ITERATIONS = 128
 FLAG_DCT = 256                    # DCT-II -> zero-pad -> DCT-III instead of the periodic FFT (library 0.7.0 on)
+FLAG_DOWNSCALE = 512              # upscale in [1/8, 1): spectrum cropped (older libraries refuse such plans: FFTUP_E_INVALID_ARG)
 
 # every symbol include/fftup.h declares
 EXPORTS = [

@@ -17,6 +17,7 @@
 #include "kernels_mixed.hpp"
 #include "kernels_dswap.hpp"
 #include "kernels_dct.hpp"
+#include "kernels_downscale.hpp"
 
 using namespace fftup;
 
@@ -111,6 +112,17 @@ int kernels_set_attributes(fftup_plan* P)
             case 4: SET_LDS(k_dct_col<4>, P->ldsCol); break;
             case 2: SET_LDS(k_dct_col<2>, P->ldsCol); break;
             default: SET_LDS(k_dct_col<1>, P->ldsCol); break;
+            }
+            return FFTUP_OK;
+        }
+        if (P->down) {                                       // (FFT downscale: kernels_downscale.hpp + the size-generic C2R)
+            if (P->half) { SET_LDS(k_row_r2c_crop<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F16>, P->ldsRowF); SET_LDS(k_row_c2r<true>, P->ldsRowI); }
+            else { SET_LDS(k_row_r2c_crop<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F32>, P->ldsRowF); SET_LDS(k_row_c2r<false>, P->ldsRowI); }
+            switch (P->TK) {
+            case 8: SET_LDS(k_col_crop<8>, P->ldsCol); break;
+            case 4: SET_LDS(k_col_crop<4>, P->ldsCol); break;
+            case 2: SET_LDS(k_col_crop<2>, P->ldsCol); break;
+            default: SET_LDS(k_col_crop<1>, P->ldsCol); break;
             }
             return FFTUP_OK;
         }
@@ -419,6 +431,56 @@ static int launch_frame_dct(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
     return FFTUP_OK;
 }
 
+// FFTUP_FLAG_DOWNSCALE (FFT mode): row R2C keeping kx <= uW/2 -> column forward / crop / inverse -> the upscale path's C2R with
+// W := uW and no read guard -> sharpen (kernels_downscale.hpp)
+static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+{
+    hipStream_t st = P->lanes[P->cur].stream;
+    const int kind = P->in_kind[in_slot];
+    if (which < 0 || which == 0) {
+        DownRowParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        p.TK = P->TK; p.NT = P->NT; p.h = (int)P->uW / 2;
+        const dim3 grid(P->H / 2, 3), block(P->thrW);
+        if (kind == 2) {
+            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
+        } else {
+            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_crop<IN_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_crop<IN_F32>, grid, block, P->ldsRowF, st, p);
+        }
+    }
+    if (which < 0 || which == 1) {
+        DownColParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
+        p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
+        const dim3 grid(P->NT, 3), block(P->thrCol);
+        switch (P->TK) {
+        case 8: hipLaunchKernelGGL(k_col_crop<8>, grid, block, P->ldsCol, st, p); break;
+        case 4: hipLaunchKernelGGL(k_col_crop<4>, grid, block, P->ldsCol, st, p); break;
+        case 2: hipLaunchKernelGGL(k_col_crop<2>, grid, block, P->ldsCol, st, p); break;
+        default: hipLaunchKernelGGL(k_col_crop<1>, grid, block, P->ldsCol, st, p); break;
+        }
+    }
+    if (which < 0 || which == 2) {
+        // W := uW: every bin k <= uW/2 is read; the empty guard [0, 0); the folded Nyquist bin is real, so the kernel's two writes
+        // of a[uW/2] (from k and from uW - k) store the same value
+        RowC2RParams p{};
+        p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->uW; p.uW = (int)P->uW;
+        p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = 0; p.zrx = 0; p.inv_norm = 1.0f / (float)P->uW; p.poly = 0;
+        const dim3 grid(P->uH / 2, 3), block(P->thrUW);
+        if (P->half) hipLaunchKernelGGL(k_row_c2r<true>, grid, block, P->ldsRowI, st, p);
+        else hipLaunchKernelGGL(k_row_c2r<false>, grid, block, P->ldsRowI, st, p);
+        P->R_valid = true;
+    }
+    if (which < 0 || which == 3) launch_sharpen(P, out_slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FFTUP_OK;
+}
+
 // -p 1: the size-generic kernels instantiated on double2 + the double sharpen
 static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
@@ -613,6 +675,7 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
     if (P->cplx) return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
     if (P->dbl) return launch_frame_f64(P, in_slot, out_slot, which);
     if (P->dct) return launch_frame_dct(P, in_slot, out_slot, which);
+    if (P->down) return launch_frame_down(P, in_slot, out_slot, which);
     if (P->tuned) {
         launch_frame_tuned(P, in_slot, out_slot, which);
         if ((which < 0 || which == 3) && !P->fused) launch_sharpen_fast(P, out_slot);

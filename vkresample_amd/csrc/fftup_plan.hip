@@ -334,14 +334,19 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     if (cfg->precision > 2) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "precision must be 0 (single), 1 (double) or 2 (half)");
     const uint32_t W = cfg->width, H = cfg->height;
     // the float -> uint32 casts below are undefined for NaN / out-of-range products: bound the inputs first
-    if (!(cfg->upscale >= 1.0f && cfg->upscale <= 64.0f)) return fail(FFTUP_E_INVALID_ARG, "upscale must be a finite number in [1, 64]");
+    // FFTUP_FLAG_DOWNSCALE: factors in [1/8, 1) instead (a factor below 1 without the flag stays an error)
+    const bool down = (cfg->flags & FFTUP_FLAG_DOWNSCALE) != 0;
+    if (down && !(cfg->upscale >= 0.125f && cfg->upscale < 1.0f)) return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the factor must lie in [0.125, 1)");
+    if (!down && !(cfg->upscale >= 1.0f && cfg->upscale <= 64.0f)) return fail(FFTUP_E_INVALID_ARG, "upscale must be a finite number in [1, 64]");
     if (W > (1u << 16) || H > (1u << 16)) return fail(FFTUP_E_INVALID_ARG, "width/height above 65536");
     if (cfg->ring > 1024) return fail(FFTUP_E_INVALID_ARG, "ring must be <= 1024");
     if (!(cfg->sharpen == cfg->sharpen)) return fail(FFTUP_E_INVALID_ARG, "sharpen is NaN");
     const uint32_t uW = (uint32_t)(cfg->upscale * (float)W);     // VkResample.cpp:1417-1418
     const uint32_t uH = (uint32_t)(cfg->upscale * (float)H);
-    if (W < 2 || H < 2 || (W & 1) || (H & 1) || (uW & 1) || (uH & 1) || uW < W || uH < H)
+    if (W < 2 || H < 2 || (W & 1) || (H & 1) || (uW & 1) || (uH & 1) || (!down && (uW < W || uH < H)))
         return fail(FFTUP_E_INVALID_ARG, "width/height (and upscaled sizes) must be even, upscale >= 1");
+    if (down && (uW < 2 || uH < 2 || uW >= W || uH >= H))
+        return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the output sizes must be at least 2 and below the input's");
     if (!is_smooth(W) || !is_smooth(H) || !is_smooth(uW) || !is_smooth(uH))
         return fail(FFTUP_E_UNSUPPORTED_SIZE, "sizes must factor into 2,3,5,7 (vkFFT.h:4719-4726)");
     // R2C rule of the reference: uW <= maxComputeSharedMemorySize/8 with 64 KB (VkResample.cpp:1424; complexSizeCalc = 16
@@ -351,6 +356,9 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     const bool dct = (cfg->flags & FFTUP_FLAG_DCT) != 0;
     if (dct && cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_DCT plans exist for -p 0 and -p 2");
     if (dct && uW > 8192u) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need an upscaled width of at most 8192");
+    // downscale plans: the same storage, the input rows in one two-buffer LDS launch (no four-step or non-R2C downscale)
+    if (down && cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_DOWNSCALE plans exist for -p 0 and -p 2");
+    if (down && W > 8192u) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DOWNSCALE plans need an input width of at most 8192");
     // (checked here, before any device access: gfx950 has 160 KB of LDS per workgroup.)  Non-R2C rows whose two Stockham
     // buffers do not fit run in ONE buffer (fft_lds_inplace: up to 16 384 complex fp32 points, 1024 threads, every stage
     // N/R <= (16/R) * 1024: radix 7 up to 14336 points, 3 and 5 up to 15360); the reference switches to multi-upload plans there (vkFFT.h:4773-4992)
@@ -383,7 +391,9 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     P->dbl = cfg->precision == 1;
     P->cplx = cplx;
     P->dct = dct;
-    P->ncols = cplx ? (int)W : (int)(W / 2 + 1);
+    P->down = down;
+    // (FFT downscale plans keep only the bins the output holds, kx <= uW/2: S1, S2 and the column pass shrink with the output)
+    P->ncols = cplx ? (int)W : (down && !dct) ? (int)(uW / 2 + 1) : (int)(W / 2 + 1);
     P->esz = P->dbl ? 8 : (P->half ? 2 : 4);
     P->csz = P->dbl ? 16 : 8;
     P->device = cfg->device;
@@ -413,8 +423,9 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         const float u = cfg->upscale;
         P->zlx = (int)(W / 2);
         P->zrx = cplx ? (int)(uint32_t)((2 * u - 1) * (float)uW / (2 * u)) : (int)(uW / 2);      // VR:1498 / VR:1493
-        P->zly = (int)(uint32_t)((float)uH / (2 * u));
-        P->zry = (int)(uint32_t)((2 * u - 1) * (float)uH / (2 * u));
+        // (downscale plans have no padding: no guard, and 2u - 1 < 0 would make the cast below undefined)
+        P->zly = down ? 0 : (int)(uint32_t)((float)uH / (2 * u));
+        P->zry = down ? 0 : (int)(uint32_t)((2 * u - 1) * (float)uH / (2 * u));
 
         P->planW = make_stage_plan(W);
         P->planH = make_stage_plan(H);
@@ -426,7 +437,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         // (experiment aot=0: the sizes with ahead-of-time kernels go through the plan-time compiler as well)
         const char* const aot_e = fftup_jit::experiment("aot");
         const bool aot = !(aot_e && atoi(aot_e) == 0);
-        P->tuned = aot && !P->dbl && !cplx && !dct && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
+        P->tuned = aot && !P->dbl && !cplx && !dct && !down && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
                    (W == 512 || W == 1024 || W == 2048) && (H == 256 || H == 512 || H == 1024);
         P->TK = 0;
         if (P->tuned) {
@@ -436,7 +447,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             // u = 2 with the symmetric guard: the polyphase column kernel (k_col_poly: forward, phase, length-H inverse in ONE buffer of
             // H TK points, odd rows out; the C2R kernel takes the even rows from S1) where its stages run in place
             const char* const poly_e = fftup_jit::experiment("generic_poly");
-            if (!cplx && !dct && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
+            if (!cplx && !dct && !down && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
                 for (int tk : {8, 4, 2, 1}) {
                     const size_t need = P->csz * (size_t)lpad_size((int)H * tk);
                     const int thr = inplace_threads(P->planH, tk, COL_INPLACE_PT, kernels_generic_max_threads(P->dbl));
@@ -454,13 +465,15 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                     if (ok) { P->TK = tk; P->ldsCol = need; P->inplaceC = true; P->thrCol = thr; break; }
                 }
             }
-            // column tile width: widest of 8,4,2,1 whose ping-pong buffers fit in LDS
+            // column tile width: widest of 8,4,2,1 whose ping-pong buffers fit in LDS (downscale plans: the forward transform,
+            // length H, is the longer one)
             if (!P->TK) for (int tk : {8, 4, 2, 1}) {
-                size_t need = 2 * P->csz * (size_t)lpad_size((int)uH * tk);
+                size_t need = 2 * P->csz * (size_t)lpad_size((int)std::max(H, uH) * tk);
                 if (need <= lds_max) { P->TK = tk; P->ldsCol = need; break; }
             }
         }
         if (!P->TK && dct) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT: the columns do not fit the LDS (no four-step DCT)"); goto bad; }
+        if (!P->TK && down) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DOWNSCALE: the columns do not fit the LDS (no four-step downscale)"); goto bad; }
         if (!P->TK) {
             // not even one column fits: tiles of one column, both column transforms in four steps through HBM (k_row4_a / k_row4_b)
             P->TK = 1; P->ldsCol = 0;
@@ -475,13 +488,13 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                 f.thrB = std::min(tmax, std::max(64, round_up(f.n2 * f.tkb / 8, 64)));
             }
         }
-        if (aot && !P->dbl && !cplx && !dct && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
+        if (aot && !P->dbl && !cplx && !dct && !down && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
             P->mixed = kernels_aot_mixed_plan(W, H);                    // 1920x1080, 1280x720
         }
         if (P->mixed) { P->TK = 4; P->ldsCol = sizeof(float2) * (size_t)H * 4; }             // k_col_m: one in-place buffer
         // any other size with an integer or half-integer upscale factor: kernels specialised for it now (the counterpart
         // of VkFFT generating its shaders at plan time)
-        if (!P->dbl && !cplx && !dct && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
+        if (!P->dbl && !cplx && !dct && !down && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
             int DD = 1;
             const int D = jit_factor(cfg->upscale, W, H, uW, uH, P->zly, P->zry, &DD);
             if (D) {
@@ -527,7 +540,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             const int tmax = kernels_generic_max_threads(P->dbl);
             P->thrW = std::min(tmax, std::max(64, round_up((int)W / 8, 64)));
             P->thrUW = std::min(tmax, std::max(64, round_up((int)uW / 8, 64)));
-            if (!(P->poly || P->inplaceC)) P->thrCol = std::min(tmax, std::max(64, round_up((int)uH * P->TK / 8, 64)));     // (in-place column plans chose theirs above)
+            if (!(P->poly || P->inplaceC)) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(H, uH) * P->TK / 8, 64)));     // (in-place column plans chose theirs above)
             // -p 1 R2C rows: one LDS buffer where every stage runs in place with 8 points per thread (two workgroups per compute unit)
             if (P->dbl && !cplx) {
                 const int tf = inplace_threads(P->planW, 1, 8, tmax), ti = inplace_threads(P->planUW, 1, 8, tmax);
@@ -613,7 +626,11 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
 {
     if (!P || !buf || !buflen) return fail(FFTUP_E_INVALID_ARG, "null argument");
     std::string s;
-    if (P->dct) s = "dct: size-generic DCT-II / zero-pad / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
+    if (P->down && P->dct) s = "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
+                               + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
+    else if (P->down) s = "downscale: size-generic kernels, spectrum cropped to " + std::to_string(P->ncols) + " columns at the row stage (LDS ping-pong, "
+                          "run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
+    else if (P->dct) s = "dct: size-generic DCT-II / zero-pad / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
                     + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
     else if (P->mixed == 3) s = "specialised at plan time: " + fftup_jit::describe(P->jit->choice);
     else if (P->tuned) s = "ahead-of-time power-of-two kernels (radix 8, 8 points per thread; fused C2R+sharpen " + std::string(P->fused ? "on" : "off") + ")"
@@ -640,7 +657,7 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     info->out_height = P->uH;
     info->num_kernels = P->fused ? 3 : 4;
     info->tuned = P->mixed == 3 ? 2 : ((P->tuned || P->mixed) ? 1 : 0);
-    // B_alg = in + 2*S1 + 2*S2 + 2*R + out
+    // B_alg = in + 2*S1 + 2*S2 + 2*R + out (FFT downscale plans: S1, S2 of the cropped uW/2 + 1 columns, P->ncols)
     const double C = 3.0, W = P->W, H = P->H, uW = P->uW, uH = P->uH;
     const bool fused_u8 = fuse_u8(P);
     const double b_in = fused_u8 ? 1.0 : (double)P->esz;
@@ -679,8 +696,8 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     info->abi_version = FFTUP_ABI_VERSION;
     info->u8_store = P->u8out ? 1 : 0;
     snprintf(info->device_name, sizeof info->device_name, "%s", device_label(P->prop));
-    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : P->cplx ? "row_c2c" : "row_r2c");
-    snprintf(info->kernel_names[1], 64, P->dct ? "dct_col_pad_idct" : "col_fwd_pad_inv");
+    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : P->down ? "row_r2c_crop" : P->cplx ? "row_c2c" : "row_r2c");
+    snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : P->down ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
     snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
     return FFTUP_OK;

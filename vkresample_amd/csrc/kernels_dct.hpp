@@ -80,14 +80,16 @@ struct DctColParams {
     float inv_norm;          // 1/H
 };
 
-// grid (ceil(W/2 / TK), 3); dynamic LDS = 2 * lpad_size(uH*TK) complex.  Sequence col of tile t: the real columns 2q, 2q+1,
+// grid (ceil(W/2 / TK), 3); dynamic LDS = 2 * lpad_size(max(H, uH)*TK) complex.  Sequence col of tile t: the real columns 2q, 2q+1,
 // q = t TK + col, as one complex sequence -- TK pairs = 2 TK floats = 8 TK contiguous bytes of every row read and written.
+// Downscale plans (uH < H, FFTUP_FLAG_DOWNSCALE): the DCT-III below reads the coefficients k < uH only -- truncation instead of
+// zero-padding, with the same loops.
 template <int TK>
 __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_dct_col(DctColParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* a = (float2*)smem;
-    float2* b = a + lpad_size(p.uH * TK);
+    float2* b = a + lpad_size(max(p.H, p.uH) * TK);
     const int tid = threadIdx.x, T = blockDim.x;
     const int tile = blockIdx.x, c = blockIdx.y;
     const int W = p.W, H = p.H, uH = p.uH;
@@ -142,7 +144,8 @@ struct IdctRowParams {
     float inv_norm;          // 1 / (W upsq): the DCT-III's 1/W and the pre-sharpen convention R = y / upsq in one constant
 };
 
-// grid (uH/2, 3); dynamic LDS = 2 * lpad_size(uW) complex.  Rows 2j (real part) and 2j+1 (imaginary part).
+// grid (uH/2, 3); dynamic LDS = 2 * lpad_size(uW) complex.  Rows 2j (real part) and 2j+1 (imaginary part).  Downscale plans
+// (uW < W): only the coefficients k < uW are loaded -- the DCT-III reads no others, and b holds lpad_size(uW) points.
 template <bool HALF_OUT>
 __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_idct_row(IdctRowParams p)
 {
@@ -153,7 +156,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_idct_row(I
     const int j = blockIdx.x, c = blockIdx.y;
     const int W = p.W, uW = p.uW;
     const float* ra = p.S2 + ((long)c * p.uH + 2 * j) * W;
-    for (int k = tid; k < W; k += T) b[lpad(k)] = make_float2(ra[k], ra[W + k]);
+    for (int k = tid; k < min(W, uW); k += T) b[lpad(k)] = make_float2(ra[k], ra[W + k]);
     __syncthreads();
     for (int k = tid; k < uW; k += T) {
         float2 w;

@@ -81,6 +81,7 @@ struct fftup_plan {
     int U = 2;                        // integer upscale factor of a polyphase plan (tuned / mixed): S1 + U-1 residue buffers
     bool cplx = false;                // non-R2C path (VR:1424 false): full complex transforms, uW beyond the R2C limit
     bool dct = false;                 // FFTUP_FLAG_DCT: DCT-II -> zero-pad -> DCT-III (kernels_dct.hpp); S1 / S2 hold real [3][H][W] / [3][uH][W]
+    bool down = false;                // FFTUP_FLAG_DOWNSCALE: uW < W, uH < H; without dct the spectrum is cropped (kernels_downscale.hpp): ncols = uW/2 + 1
     bool poly = false;                         // size-generic u = 2 plan: polyphase column kernel (k_col_poly), the C2R kernel reads the even rows from S1
     bool inplaceC = false;                     // -p 1 R2C plans: the column kernel's two transforms in one LDS buffer (k_col<TK, double2, true>)
     bool inplaceF = false, inplaceI = false;   // ... whose forward / inverse rows are too long for two LDS buffers: fft_lds_inplace
