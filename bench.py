@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the upscale hot path (BASELINE.json metric).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
@@ -14,7 +14,13 @@ fixed).  The K-step timed region (barrier + synchronize on both sides, MAX over 
 Rank 0 prints ONE JSON line.  --dump-outputs DIR writes what the last timed step computed (the output frames a caller would
 download) as DIR/<name>.npy, see dump_outputs().
 
-At N = 1 the same invocation also times, briefly, the other single-GPU BASELINE configurations and the reference's own
+A plain run does only what `value` needs: plan, resident frames, warm-up, the timed regions, --dump-outputs, the line.  Everything
+that takes work or runs of its own comes with --full: the untimed step of per-kernel events (`kernel_ms_timed_region`), the
+kernels timed one at a time (`kernel_ms`, `roofline`), HBM bytes and vector-instruction counts (committed and, at N = 1, measured
+live under rocprofv3), socket power and clock during the timed regions (`power`), the CPU baseline, the reference Vulkan figure,
+the RCCL bring-up and, at N = 1, `others` below.  The timed steps are the same either way.
+
+With --full, at N = 1 the same invocation also times, briefly, the other single-GPU BASELINE configurations and the reference's own
 `-n 1000` figure (`others`: config3 = -p 2 with the fused uint8 load, config4 = 1920x1080, execute_n1000 =
 fftup_execute(plan, 1000) on a plan without a ring of slots, i.e. performVulkanUpscale(..., 1000), VkResample.cpp:1260-1278).
 `--preset config5` (BASELINE's 512-frame batch over 8 GPUs) carries the job accounting: every rank processes the frames
@@ -65,13 +71,17 @@ def parse_args():
     ap.add_argument("--fuse-u8-store", action="store_true", help="the fused C2R+sharpen kernel stores 8-bit RGB (FFTUP_FLAG_FUSE_U8_STORE): 8-bit in, 8-bit out")
     ap.add_argument("--generic", action="store_true", help="size-generic kernels (FFTUP_FLAG_GENERIC_KERNELS): no tuned, no plan-time specialised plan")
     ap.add_argument("--tune", action="store_true", help="FFTUP_FLAG_TUNE_PLAN: plan-time tuner for sizes specialised at plan time")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-rccl-check", action="store_true", help="skip the one-rank RCCL bring-up of N = 1 lines (`rccl_selfcheck`)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides `value`, everything else the line can carry: per-kernel times, roofline, HBM traffic (live at N = 1), "
+                         "power, CPU baseline, reference figure, RCCL bring-up, the other BASELINE configurations (`others`) -- "
+                         "each of these can still be left out with its --no-* option")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline (`cpu_baseline`)")
+    ap.add_argument("--no-rccl-check", action="store_true", help="with --full: skip the one-rank RCCL bring-up of N = 1 lines (`rccl_selfcheck`)")
     ap.add_argument("--no-live-traffic", action="store_true",
-                    help="skip the two short rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over this very configuration that measure "
+                    help="with --full: skip the two short rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) over this very configuration that measure "
                          "`roofline.traffic` live at N = 1; the committed figures of profiles/hbm_traffic.json are reported instead")
     ap.add_argument("--cpu-frames", type=int, default=24, help="frames of the bounded CPU-baseline sample (~11 s on 128 threads)")
-    ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other BASELINE configurations (`others`)")
+    ap.add_argument("--no-others", action="store_true", help="with --full: skip the short runs of the other BASELINE configurations (`others`)")
     ap.add_argument("--job", action="store_true",
                     help="job accounting: rank r processes frames shard.frames_for_rank(frames_per_step * world, world, r), all distinct "
                          "(needs --ring >= --frames-per-step), output checksums reduced over the ranks (implied by --preset config5)")
@@ -79,8 +89,9 @@ def parse_args():
                     help="with --job: dynamic sharding -- ranks claim chunks of frames from one shared counter (shard.FrameQueue, "
                          "torch.distributed's store) instead of the static stripe; every rank keeps all frames of a step resident")
     ap.add_argument("--queue-chunk", type=int, default=8, help="frames per claim of --queue")
-    ap.add_argument("--profile-iters", type=int, default=50)
-    ap.add_argument("--event-stride", type=int, default=32, help="kernel-timing events on every n-th frame of the first timed region")
+    ap.add_argument("--profile-iters", type=int, default=50, help="with --full: iterations of the kernels timed one at a time (`kernel_ms`)")
+    ap.add_argument("--event-stride", type=int, default=32,
+                    help="with --full: kernel-timing events on every n-th frame of the untimed step before the timed regions")
     ap.add_argument("--streams", type=int, default=3,
                     help="HIP streams (lanes) consecutive frames alternate on; 1 = strictly sequential kernels")
     ap.add_argument("--host-streamed", action="store_true",
@@ -388,7 +399,8 @@ def live_traffic(argv_config):
     """HBM bytes per launch of this configuration's kernels, measured NOW: two short runs of this script under
     `rocprofv3 --pmc` (FETCH_SIZE and WRITE_SIZE do not fit one pass; counters only, with --kernel-trace, as the microarchitecture
     guide prescribes), averaged per kernel over the run's launches, corrected as PMC_KERNELS says.  None where rocprofv3 is missing,
-    fails or takes too long -- the committed figures then stand in (`traffic_source` says which it is)."""
+    fails or takes too long -- the committed figures then stand in (`traffic_source` says which it is).  The runs are --full ones
+    (the events step and the kernels one at a time launch too), like those of tools/gpu_pmc.sh the committed figures come from."""
     import csv
     import glob
     import shutil
@@ -398,7 +410,7 @@ def live_traffic(argv_config):
         return None, "rocprofv3 not found"
     if any(k.startswith(("ROCPROF", "ROCP_")) for k in os.environ) or "rocprof" in os.environ.get("LD_PRELOAD", ""):
         return None, "this run is itself being profiled"
-    child = [sys.executable, os.path.abspath(__file__)] + argv_config + ["--steps", "1", "--warmup", "1", "--repeats", "1", "--frames-per-step", "8",
+    child = [sys.executable, os.path.abspath(__file__)] + argv_config + ["--full", "--steps", "1", "--warmup", "1", "--repeats", "1", "--frames-per-step", "8",
                                                                         "--profile-iters", "2", "--no-cpu-baseline", "--no-others", "--no-rccl-check", "--no-live-traffic"]
     acc = {}
     t0 = time.perf_counter()
@@ -531,10 +543,12 @@ def main():
     if v.device_count() < 1:
         raise SystemExit("bench.py needs a HIP device (the product has no CPU path)")
     dev = local_rank % v.device_count()
-    try:
-        n_cu = torch.cuda.get_device_properties(dev).multi_processor_count if torch.cuda.is_available() else None
-    except Exception:
-        n_cu = None
+    n_cu = None
+    if args.full:
+        try:
+            n_cu = torch.cuda.get_device_properties(dev).multi_processor_count if torch.cuda.is_available() else None
+        except Exception:
+            pass
     flags = (v.FLAG_FUSE_U8_LOAD if args.fuse_u8 else 0) | (v.FLAG_GENERIC_KERNELS if args.generic else 0) | (v.FLAG_TUNE_PLAN if args.tune else 0) | \
             (v.FLAG_FUSE_U8_STORE if args.fuse_u8_store else 0)
     up = v.Upscaler(args.width, args.height, args.upscale, args.precision, 0.2, dev, flags, args.ring)
@@ -626,13 +640,15 @@ def main():
 
     kms = [0.0] * len(up.kernel_names)
     if not args.host_streamed and not args.queue:
-        # HIP events before/after every kernel launch of every --event-stride-th frame, on the stream that runs it: one step of its
-        # own, untimed (the events are not part of the path the timed steps measure)
-        _, kms = up.execute_ring_timed(args.frames_per_step, slot, args.event_stride)   # blocks until the batch is done
+        if args.full:
+            # HIP events before/after every kernel launch of every --event-stride-th frame, on the stream that runs it: one step of
+            # its own, untimed (the events are not part of the path the timed steps measure)
+            _, kms = up.execute_ring_timed(args.frames_per_step, slot, args.event_stride)   # blocks until the batch is done
+        # (without --full as well: the timed steps start at the same slot either way)
         slot = (slot + args.frames_per_step) % args.ring
 
     # ---- timed regions: EXACTLY --steps steps each, barrier + synchronize on both sides, MAX over ranks; median of --repeats
-    power = PowerSampler(v.device_pci_bus_id(dev)).start() if rank == 0 else None
+    power = PowerSampler(v.device_pci_bus_id(dev)).start() if rank == 0 and args.full else None
     region_s, region_dev_ms, region_own_s = [], [], []
     last_slots = []                            # output slots the step that ran last wrote, in order
     for rep in range(max(1, args.repeats)):
@@ -723,39 +739,8 @@ def main():
                          else "frame f*world + rank (VkResample.cpp:1622-1629)"}
     line = None
     if rank == 0:
-        # kms: average kernel durations in the untimed step of per-kernel events before the timed regions, launched as the timed
-        # steps launch them (consecutive frames overlap on --streams lanes, so a kernel's duration there includes the time it shares
-        # the GPU with the other lanes' kernels);
-        # iso: the same kernels launched strictly one after the other right after the timed regions, HIP events on the
-        # launching stream, net of the cost of an empty event pair (= what rocprofv3 --kernel-trace --stats reports)
-        iso = up.profile_kernels(args.profile_iters)
-        if max(iso) <= 0:                      # kernels shorter than an event pair's own cost (tiny frames, few iterations)
-            iso = list(kms)
-        dom = max(range(len(iso)), key=lambda i: iso[i])
-        achieved = up.kernel_alg_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 1e9
-        if args.host_streamed or args.queue:
-            kms = list(iso)                   # no per-kernel events in the streamed loop
-        achieved_ovl = up.kernel_alg_bytes[dom] / (kms[dom] * 1e-3) / 1e9 if kms[dom] > 0 else None
         frame_ms = region_dev_ms[med] / (args.steps * args.frames_per_step)
         wall_frame_ms = dt / (args.steps * args.frames_per_step) * 1e3
-        # measured HBM bytes (rocprofv3 --pmc, corrected as profiles/hbm_traffic.json documents) -- static: taken from the
-        # committed profile of THIS configuration, not re-measured by this run
-        key = config_key(args) + ("_u8out" if up.u8_store else "")
-        per, frame_hbm, tsrc = frame_traffic(args.traffic_json, key, up.kernel_names)
-        traffic = per.get(up.kernel_names[dom]) if per else None
-        static_traffic, live = traffic, None
-        if world == 1 and not args.no_live_traffic and not args.host_streamed and not args.queue:
-            # ... and measured now (the static figures stay in the line for comparison)
-            cfg_argv = ["--width", str(args.width), "--height", str(args.height), "--upscale", repr(args.upscale), "--precision", str(args.precision),
-                        "--ring", str(args.ring), "--streams", str(args.streams)] + (["--fuse-u8"] if args.fuse_u8 else []) + \
-                       (["--fuse-u8-store"] if args.fuse_u8_store else []) + (["--generic"] if args.generic else [])
-            live, live_src = live_traffic(cfg_argv)
-            if live and all(n in live for n in up.kernel_names if n != "-"):
-                per = {n: live[n]["hbm_bytes_per_launch"] for n in up.kernel_names if n != "-"}
-                frame_hbm, tsrc, traffic = sum(per.values()), live_src, per[up.kernel_names[dom]]
-            else:
-                tsrc = (tsrc or "none") + " [live measurement unavailable: %s]" % (live_src if not live else "kernels missing")
-                live = None
         esz = {0: 4, 1: 8, 2: 2}[args.precision]
         b_in = 1 if (args.fuse_u8 and args.precision != 1) else esz
         b_min = 3.0 * (args.width * args.height * b_in + up.out_width * up.out_height * (1 if up.u8_store else esz))
@@ -779,33 +764,67 @@ def main():
             "ms_per_frame": wall_frame_ms, "ms_per_frame_device_events": frame_ms,
             "frame_alg_bytes": up.alg_bytes_per_frame, "B_min": b_min, "b_min_frac": b_min / (wall_frame_ms * 1e-3) / 8e12,
             "frame_roofline_frac": up.alg_bytes_per_frame / (wall_frame_ms * 1e-3) / 8e12,
-            "frame_hbm_bytes_measured": frame_hbm,
-            "real_traffic_frac": (frame_hbm / (wall_frame_ms * 1e-3) / 8e12) if frame_hbm else None,
-            "kernel_ms": dict(zip(up.kernel_names, iso)),
-            "kernel_ms_timed_region": dict(zip(up.kernel_names, kms)),
-            "roofline": {"bound": "hbm", "kernel": up.kernel_names[dom], "achieved": achieved, "peak": 8000.0,
-                         "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": tsrc,
-                         # the same kernel priced by the bytes it really has to move (a fused launch never writes R)
-                         "achieved_real_bytes": up.kernel_min_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 1e9,
-                         "frac_real_bytes": up.kernel_min_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 8e12,
-                         "achieved_overlapped": achieved_ovl,
-                         "frame_achieved": up.alg_bytes_per_frame / (wall_frame_ms * 1e-3) / 1e9,      # per GPU
-                         "frame_frac": up.alg_bytes_per_frame / (wall_frame_ms * 1e-3) / 8e12,
-                         # do the static figures (traffic, vector instructions) belong to the kernel sources that just ran?
-                         "traffic_kernel_sources_current": traffic_is_current(args.traffic_json, key),
-                         "traffic_static": static_traffic, "traffic_live": live},
         }
-        # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this configuration, when there is one
-        rp_us, rp_file, rp_fresh = rocprof_kernel_us(key, up.kernel_names[dom])
-        if rp_us:
-            line["roofline"].update({"rocprof_avg_us": rp_us, "frac_rocprof": up.kernel_alg_bytes[dom] / (rp_us * 1e-6) / 8e12,
-                                     "rocprof_source": rp_file, "rocprof_kernel_sources_current": rp_fresh})
-        fvi, vbusy = valu_busy(args.traffic_json, key, up.kernel_names, wall_frame_ms, (power_stats or {}).get("sclk_mhz_median"), n_cu)
-        line["frame_valu_insts"], line["valu_busy_frac"] = fvi, vbusy
-        if power_stats and power_stats.get("socket_power_w_median"):
-            # at the power limit this is the number a kernel change has to move: joules per frame
-            power_stats["energy_mj_per_frame"] = power_stats["socket_power_w_median"] * wall_frame_ms       # (one GPU works on a frame)
-        line["power"] = power_stats
+        if args.full:
+            # kms: average kernel durations in the untimed step of per-kernel events before the timed regions, launched as the timed
+            # steps launch them (consecutive frames overlap on --streams lanes, so a kernel's duration there includes the time it shares
+            # the GPU with the other lanes' kernels);
+            # iso: the same kernels launched strictly one after the other right after the timed regions, HIP events on the
+            # launching stream, net of the cost of an empty event pair (= what rocprofv3 --kernel-trace --stats reports)
+            iso = up.profile_kernels(args.profile_iters)
+            if max(iso) <= 0:                      # kernels shorter than an event pair's own cost (tiny frames, few iterations)
+                iso = list(kms)
+            dom = max(range(len(iso)), key=lambda i: iso[i])
+            achieved = up.kernel_alg_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 1e9
+            if args.host_streamed or args.queue:
+                kms = list(iso)                   # no per-kernel events in the streamed loop
+            achieved_ovl = up.kernel_alg_bytes[dom] / (kms[dom] * 1e-3) / 1e9 if kms[dom] > 0 else None
+            # measured HBM bytes (rocprofv3 --pmc, corrected as profiles/hbm_traffic.json documents) -- static: taken from the
+            # committed profile of THIS configuration, not re-measured by this run
+            key = config_key(args) + ("_u8out" if up.u8_store else "")
+            per, frame_hbm, tsrc = frame_traffic(args.traffic_json, key, up.kernel_names)
+            traffic = per.get(up.kernel_names[dom]) if per else None
+            static_traffic, live = traffic, None
+            if world == 1 and not args.no_live_traffic and not args.host_streamed and not args.queue:
+                # ... and measured now (the static figures stay in the line for comparison)
+                cfg_argv = ["--width", str(args.width), "--height", str(args.height), "--upscale", repr(args.upscale), "--precision", str(args.precision),
+                            "--ring", str(args.ring), "--streams", str(args.streams)] + (["--fuse-u8"] if args.fuse_u8 else []) + \
+                           (["--fuse-u8-store"] if args.fuse_u8_store else []) + (["--generic"] if args.generic else [])
+                live, live_src = live_traffic(cfg_argv)
+                if live and all(n in live for n in up.kernel_names if n != "-"):
+                    per = {n: live[n]["hbm_bytes_per_launch"] for n in up.kernel_names if n != "-"}
+                    frame_hbm, tsrc, traffic = sum(per.values()), live_src, per[up.kernel_names[dom]]
+                else:
+                    tsrc = (tsrc or "none") + " [live measurement unavailable: %s]" % (live_src if not live else "kernels missing")
+                    live = None
+            line.update({
+                "frame_hbm_bytes_measured": frame_hbm,
+                "real_traffic_frac": (frame_hbm / (wall_frame_ms * 1e-3) / 8e12) if frame_hbm else None,
+                "kernel_ms": dict(zip(up.kernel_names, iso)),
+                "kernel_ms_timed_region": dict(zip(up.kernel_names, kms)),
+                "roofline": {"bound": "hbm", "kernel": up.kernel_names[dom], "achieved": achieved, "peak": 8000.0,
+                             "unit": "GB/s", "frac": achieved / 8000.0, "traffic": traffic, "traffic_source": tsrc,
+                             # the same kernel priced by the bytes it really has to move (a fused launch never writes R)
+                             "achieved_real_bytes": up.kernel_min_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 1e9,
+                             "frac_real_bytes": up.kernel_min_bytes[dom] / (max(iso[dom], 1e-6) * 1e-3) / 8e12,
+                             "achieved_overlapped": achieved_ovl,
+                             "frame_achieved": up.alg_bytes_per_frame / (wall_frame_ms * 1e-3) / 1e9,      # per GPU
+                             "frame_frac": up.alg_bytes_per_frame / (wall_frame_ms * 1e-3) / 8e12,
+                             # do the static figures (traffic, vector instructions) belong to the kernel sources that just ran?
+                             "traffic_kernel_sources_current": traffic_is_current(args.traffic_json, key),
+                             "traffic_static": static_traffic, "traffic_live": live},
+            })
+            # the same fraction from the committed rocprofv3 --kernel-trace --stats summary of this configuration, when there is one
+            rp_us, rp_file, rp_fresh = rocprof_kernel_us(key, up.kernel_names[dom])
+            if rp_us:
+                line["roofline"].update({"rocprof_avg_us": rp_us, "frac_rocprof": up.kernel_alg_bytes[dom] / (rp_us * 1e-6) / 8e12,
+                                         "rocprof_source": rp_file, "rocprof_kernel_sources_current": rp_fresh})
+            fvi, vbusy = valu_busy(args.traffic_json, key, up.kernel_names, wall_frame_ms, (power_stats or {}).get("sclk_mhz_median"), n_cu)
+            line["frame_valu_insts"], line["valu_busy_frac"] = fvi, vbusy
+            if power_stats and power_stats.get("socket_power_w_median"):
+                # at the power limit this is the number a kernel change has to move: joules per frame
+                power_stats["energy_mj_per_frame"] = power_stats["socket_power_w_median"] * wall_frame_ms       # (one GPU works on a frame)
+            line["power"] = power_stats
         if dumped is not None:
             line["dump_outputs"] = dumped
         if args.host_streamed:
@@ -825,13 +844,13 @@ def main():
             line["rccl_ranks"] = job["collective_ranks"]
             line["frames_done"] = job["frames_done"]
             line["checksum"] = job["checksum"]
-        if not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
+        if args.full and not args.no_cpu_baseline and world == 1:      # reported on rank 0 at N = 1 only
             line["cpu_baseline"] = cpu_baseline(args)
             line["reference_vulkan_baseline"] = reference_vulkan_baseline(args)
-        if world == 1 and not args.no_rccl_check and torch.cuda.is_available():
+        if args.full and world == 1 and not args.no_rccl_check and torch.cuda.is_available():
             line["rccl_selfcheck"] = rccl_selfcheck(dev)
     up.close()
-    if rank == 0 and world == 1 and not args.no_others and not args.host_streamed and (args.preset or "config2") == "config2" \
+    if args.full and rank == 0 and world == 1 and not args.no_others and not args.host_streamed and (args.preset or "config2") == "config2" \
             and (args.width, args.height, args.precision) == (2048, 1024, 0):
         line["others"] = o = other_configs(v, synth, dev, args.traffic_json, n_cu, live=not args.no_live_traffic)
         # the figures a reader of the one line needs without opening `others`: the reference's -n 1000 number per configuration

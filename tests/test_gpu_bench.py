@@ -20,11 +20,11 @@ def _line(out):
 
 @pytest.fixture(scope="module")
 def bench_line():
-    """ONE run of `python bench.py` as the driver runs it (no cache dir pinned), shared by the tests below: the line's contract is
+    """ONE run of `python bench.py --full` (no cache dir pinned), shared by the tests below: the line's contract is
     asserted hard, what depends on this box's speed, on rocprofv3 / RCCL coming up, or on the committed profiles being current is
     reported as an expected failure with its reason (pytest -x does not stop there: the parity record stands either way)."""
     env = {k: v for k, v in os.environ.items() if k != "FFTUP_CACHE_DIR"}
-    r = subprocess.run([sys.executable, "bench.py", "--steps", "2", "--warmup", "1", "--repeats", "3", "--frames-per-step", "64",
+    r = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "2", "--warmup", "1", "--repeats", "3", "--frames-per-step", "64",
                         "--cpu-frames", "1", "--profile-iters", "5"], cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     return _line(r.stdout)
@@ -136,6 +136,22 @@ def test_bench_line_rccl_selfcheck(bench_line):
     """every N = 1 line brings RCCL up as a one-rank communicator on this GPU (the library the N > 1 runs depend on)"""
     chk = bench_line["rccl_selfcheck"]
     _soft(chk.get("ok") is True and chk.get("ranks") == 1, "RCCL did not come up in the bench line: %s" % chk)
+
+
+def test_bench_plain_line_is_the_headline_alone():
+    """`python bench.py` without --full, as the driver runs it: the headline's fields mean what they mean in a --full line, and
+    nothing that takes runs of its own (kernels one at a time, live counters, CPU baseline, RCCL, other configurations) is in it"""
+    env = {k: v for k, v in os.environ.items() if k != "FFTUP_CACHE_DIR"}
+    r = subprocess.run([sys.executable, "bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--frames-per-step", "64"],
+                       cwd=ROOT, capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    d = _line(r.stdout)
+    assert d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1 and d["unit"] == "frames/s" and d["higher_is_better"] is True
+    assert d["metric"].startswith("frames/s, 2048x1024->4096x2048 fp32") and d["dtype"] == "f32" and d["config"]["preset"] == "config2"
+    assert d["value"] > 1000 and abs(d["value"] - 2 * 64 / d["timed_region_s_median"]) < 1e-6 * d["value"]
+    assert len(d["region_s"]) == 1 and abs(d["ms_per_step"] - d["timed_region_s_median"] * 1e3 / 2) < 1e-9 * d["ms_per_step"]
+    assert not set(d) & {"kernel_ms", "kernel_ms_timed_region", "roofline", "power", "frame_hbm_bytes_measured", "cpu_baseline",
+                         "reference_vulkan_baseline", "rccl_selfcheck", "others", "execute_n1000"}
 
 
 @pytest.mark.parametrize("png", [False, True])

@@ -225,6 +225,16 @@ def test_bench_gpus_flag_starts_ranks_itself():
         assert r.returncode != 0 or json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])["n_gpus"] == 2
 
 
+def test_bench_full_is_off_by_default(monkeypatch):
+    """a plain `bench.py` line is the headline alone; the figures that take runs of their own come with --full"""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse_args().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-others"])
+    a = bench.parse_args()
+    assert a.full is True and a.no_others is True
+
+
 def test_static_counter_figures_belong_to_these_kernel_sources():
     """bench.py prints HBM bytes and vector-instruction counts from committed rocprofv3 --pmc runs (profiles/hbm_traffic.json) and
     a second roofline fraction from the committed --kernel-trace --stats summaries (profiles/kernel_stats_index.json): both carry

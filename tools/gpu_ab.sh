@@ -28,6 +28,6 @@ print({r['Name'].split('(')[0].replace('void fftup::', '')[:48]: round(float(r['
        for r in csv.DictReader(open(f)) if 'fftup' in r['Name'] and 'unpack' not in r['Name']})
 PY
   else
-    env $envs python bench.py --steps 5 --warmup 1 --repeats 3 --no-cpu-baseline --no-others $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.4f ms/frame'%d['ms_per_frame'], {k:round(v*1e3,1) for k,v in d['kernel_ms'].items()})"
+    env $envs python bench.py --full --steps 5 --warmup 1 --repeats 3 --no-cpu-baseline --no-others $BENCH_ARGS 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('%.4f ms/frame'%d['ms_per_frame'], {k:round(v*1e3,1) for k,v in d['kernel_ms'].items()})"
   fi
 done; done

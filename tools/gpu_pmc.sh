@@ -5,8 +5,10 @@ TAG=${1:-pmc}; shift
 OUT=$GRAFT_REPO_ROOT/gpurun_out/$TAG
 mkdir -p $OUT
 export TMPDIR=/tmp
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp
-BENCH="python $GRAFT_REPO_ROOT/bench.py --steps 1 --warmup 1 --repeats 1 --frames-per-step 8 --profile-iters 2 --no-cpu-baseline --no-others --no-live-traffic --no-rccl-check $@"
+# (--full: the same launches as the live passes of bench.py --full, events step and kernels one at a time included)
+BENCH="python $ROOT/bench.py --full --steps 1 --warmup 1 --repeats 1 --frames-per-step 8 --profile-iters 2 --no-cpu-baseline --no-others --no-live-traffic --no-rccl-check $@"
 i=0
 for SET in \
   "SQ_WAVES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS GRBM_GUI_ACTIVE" \

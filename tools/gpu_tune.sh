@@ -7,7 +7,7 @@ for cfg in "640 480 2" "720 480 2" "800 600 2" "1000 1000 2" "1440 900 2" "1600 
   set -- $cfg
   for mode in default tuned; do
     if [ $mode = tuned ]; then export FFTUP_LIBRARY=$GRAFT_REPO_ROOT/vkresample_amd/libfftup_knobs.so FFTUP_EXPERIMENT=jit_tune=1 FFTUP_JIT_VERBOSE=1; else unset FFTUP_EXPERIMENT FFTUP_JIT_VERBOSE; rm -f $FFTUP_CACHE_DIR/wisdom.txt; fi
-    python bench.py --width $1 --height $2 --upscale $3 --no-cpu-baseline --steps 3 --warmup 1 --repeats 3 --frames-per-step 256 --ring 4 > $OUT/b_$1x$2_u$3_$mode.json 2> $OUT/err_$1x$2_u$3_$mode.txt
+    python bench.py --full --width $1 --height $2 --upscale $3 --no-cpu-baseline --steps 3 --warmup 1 --repeats 3 --frames-per-step 256 --ring 4 > $OUT/b_$1x$2_u$3_$mode.json 2> $OUT/err_$1x$2_u$3_$mode.txt
     grep "fftup: tuning" $OUT/err_$1x$2_u$3_$mode.txt | sed 's/^/    /'
     python - $OUT/b_$1x$2_u$3_$mode.json $mode <<'PY'
 import json,sys

@@ -7,7 +7,7 @@ for cfg in "1280 720 1.5" "1920 1080 1.5" "2560 1440 1.5" "2048 1024 1.5" "640 4
   set -- $cfg
   for mode in jit generic; do
     if [ $mode = generic ]; then FL="--generic"; else FL=""; fi
-    python bench.py --width $1 --height $2 --upscale $3 --no-cpu-baseline --steps 3 --warmup 1 --repeats 3 --frames-per-step 256 --ring 4 $FL > $OUT/b_$1x$2_u$3_$mode.json 2>> $OUT/err.txt
+    python bench.py --full --width $1 --height $2 --upscale $3 --no-cpu-baseline --steps 3 --warmup 1 --repeats 3 --frames-per-step 256 --ring 4 $FL > $OUT/b_$1x$2_u$3_$mode.json 2>> $OUT/err.txt
     python - $OUT/b_$1x$2_u$3_$mode.json <<'PY'
 import json,sys
 try:
