@@ -32,7 +32,9 @@ enum {
     FFTUP_OK = 0,
     FFTUP_E_INVALID_ARG = 1,    /* null pointer, bad slot, odd size, channels != 3 (VR:1368)            */
     FFTUP_E_UNSUPPORTED_SIZE = 2, /* a dimension is not 2,3,5,7-smooth: VF:4719-4726
-                                     (VK_ERROR_FORMAT_NOT_SUPPORTED)                                   */
+                                     (VK_ERROR_FORMAT_NOT_SUPPORTED); with FFTUP_FLAG_ANY_SIZE: such a
+                                     dimension is longer than 4096, or the plan is outside that flag's
+                                     bounds (fftup_last_error says which)                              */
     FFTUP_E_UNSUPPORTED_PRECISION = 3, /* -p must be 0, 1 or 2                                         */
     FFTUP_E_NO_DEVICE = 4,      /* no HIP device / bad device id (VR:1292-1296)                         */
     FFTUP_E_HIP = 5,            /* a HIP runtime call failed (message in fftup_last_error)              */
@@ -85,7 +87,7 @@ enum {
                                         Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), u*W <= 8192 and columns
                                         whose transforms fit the compute unit's local memory (no four-step DCT):
                                         FFTUP_E_UNSUPPORTED_SIZE otherwise                                                     */
-    FFTUP_FLAG_DOWNSCALE = 512u      /* EXTENSION: spectral DOWNSCALE, upscale in [0.125, 1) (FFTUP_E_INVALID_ARG otherwise; without
+    FFTUP_FLAG_DOWNSCALE = 512u,     /* EXTENSION: spectral DOWNSCALE, upscale in [0.125, 1) (FFTUP_E_INVALID_ARG otherwise; without
                                         the flag a factor below 1 stays FFTUP_E_INVALID_ARG, so a library without this mode refuses
                                         such a plan).  Output sizes by the usual rule uW = (uint32_t)(u W), uH = (uint32_t)(u H) in
                                         fp32: even, at least 2 and below W, H (FFTUP_E_INVALID_ARG), 2,3,5,7-smooth
@@ -103,6 +105,29 @@ enum {
                                         _GENERIC_KERNELS, _UNFUSED_SHARPEN and _TUNE_PLAN are accepted and change nothing).
                                         Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), W <= 8192 and columns whose
                                         transforms fit the compute unit's local memory: FFTUP_E_UNSUPPORTED_SIZE otherwise       */
+    FFTUP_FLAG_ANY_SIZE = 1024u      /* EXTENSION: widens the set of accepted SIZES and changes nothing else.  Without the flag: the
+                                        reference's rule, every length (W, H, uW, uH) 2,3,5,7-smooth.  With it, on a plan whose four
+                                        lengths are smooth: a no-op -- same kernels (ahead-of-time and plan-time ones included), same
+                                        fftup_info, same output bytes.  Otherwise: the lengths still have to be even and at least 2
+                                        (uW = (uint32_t)(u W), uH = (uint32_t)(u H); odd: FFTUP_E_INVALID_ARG), and a length with a
+                                        prime factor above 7 is accepted if it is at most 4096 (beyond: FFTUP_E_UNSUPPORTED_SIZE).
+                                        Such a transform runs as a chirp-z (Bluestein) transform through a smooth length
+                                        L >= 2N - 1 (L <= 8192); the smooth lengths of the same plan keep their Stockham transforms.
+                                        The result is the reference's filter at that size, per axis and separable: forward DFT, the
+                                        centred zero-pad with quirks B1-B3, inverse DFT, then the sharpen pass unchanged (B4, B5,
+                                        upsq = "%f"(u u)).  With FFTUP_FLAG_DOWNSCALE (FFT mode): that flag's formula, W <= 8192.
+                                        A plan with a non-smooth length runs the size-generic R2C kernels (fftup_info.tuned =
+                                        u8_store = 0, kernel names with a "_bz" suffix where a Bluestein transform runs;
+                                        FFTUP_FLAG_FUSE_U8_STORE, _GENERIC_KERNELS, _UNFUSED_SHARPEN and _TUNE_PLAN are accepted and
+                                        change nothing; FFTUP_FLAG_FUSE_U8_LOAD and every execution path work as on other plans), and
+                                        is accepted for -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), rows of at most 8192
+                                        points and columns whose transforms fit the compute unit's local memory (no non-R2C or
+                                        four-step path beside a Bluestein transform: FFTUP_E_UNSUPPORTED_SIZE).  With FFTUP_FLAG_DCT
+                                        a non-smooth length stays FFTUP_E_UNSUPPORTED_SIZE (the DCT kernels' 2N / 4N packing is not
+                                        covered), with or without FFTUP_FLAG_DOWNSCALE.  All of this is arithmetic on the sizes,
+                                        decided before any device access.  fftup_jit_check keeps returning FFTUP_E_UNSUPPORTED_SIZE
+                                        for these sizes, and fftup_version() is unchanged: detect the mode by creating a plan -- a
+                                        library without it returns FFTUP_E_UNSUPPORTED_SIZE for 46x22 with the flag set         */
 };
 
 /* Replaces VkResampleConfiguration (VR:45-59) + the part of VkFFTConfiguration (VF:22-94) that
@@ -164,7 +189,8 @@ FFTUP_API int fftup_device_pci_bus_id(int device, char* buf, size_t buflen);
  * even and smooth is a valid plan, as in the reference: upscaled widths beyond 8192 (4096 for -p 1) take the reference's
  * non-R2C path (VR:1424); rows and columns too long for the compute unit's local memory run as two-launch "four-step"
  * transforms through device memory (the reference's multi-upload plans, VF:4773-4992).  fftup_plan_describe says which.
- * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag); FFTUP_FLAG_DOWNSCALE plans take factors below 1. */
+ * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag); FFTUP_FLAG_DOWNSCALE plans take factors below 1;
+ * FFTUP_FLAG_ANY_SIZE lifts the smoothness rule for even lengths up to 4096 (Bluestein transforms, see the flag). */
 FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);

@@ -43,7 +43,8 @@ def device_pci_bus_id(device=0):
 
 
 class Upscaler:
-    """One plan = one (width, height, upscale, precision, sharpen, device) configuration."""
+    """One plan = one (width, height, upscale, precision, sharpen, device) configuration.  `flags`: the FLAG_* bits of _lib
+    (include/fftup.h), e.g. FLAG_ANY_SIZE (1024) for even sizes that do not factor into 2,3,5,7."""
 
     def __init__(self, width, height, upscale=2.0, precision=0, sharpen=0.2, device=0, flags=0, ring=1):
         self._lib = _lib.load()
@@ -65,6 +66,7 @@ class Upscaler:
         self.kernel_alg_bytes = list(info.kernel_alg_bytes)
         self.kernel_min_bytes = list(info.kernel_min_bytes)
         self.kernel_names = [bytes(n).split(b"\0")[0].decode() for n in info.kernel_names]
+        self.num_kernels = info.num_kernels
         self.device_name = info.device_name.decode()
         self.device_bytes = info.device_bytes
         self.tuned = bool(info.tuned)

@@ -18,6 +18,7 @@
 #include "kernels_dswap.hpp"
 #include "kernels_dct.hpp"
 #include "kernels_downscale.hpp"
+#include "kernels_bluestein.hpp"
 
 using namespace fftup;
 
@@ -116,9 +117,23 @@ int kernels_set_attributes(fftup_plan* P)
             return FFTUP_OK;
         }
         if (P->down) {                                       // (FFT downscale: kernels_downscale.hpp + the size-generic C2R)
-            if (P->half) { SET_LDS(k_row_r2c_crop<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F16>, P->ldsRowF); SET_LDS(k_row_c2r<true>, P->ldsRowI); }
-            else { SET_LDS(k_row_r2c_crop<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F32>, P->ldsRowF); SET_LDS(k_row_c2r<false>, P->ldsRowI); }
-            switch (P->TK) {
+            // (FFTUP_FLAG_ANY_SIZE: the instantiations with a Bluestein transform, where this plan launches them)
+            if (P->bzW.L) {
+                if (P->half) { SET_LDS((k_row_r2c_crop<IN_F16, true>), P->ldsRowF); SET_LDS((k_row_r2c_crop<IN_U8_F16, true>), P->ldsRowF); }
+                else { SET_LDS((k_row_r2c_crop<IN_F32, true>), P->ldsRowF); SET_LDS((k_row_r2c_crop<IN_U8_F32, true>), P->ldsRowF); }
+            }
+            else if (P->half) { SET_LDS(k_row_r2c_crop<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F16>, P->ldsRowF); }
+            else { SET_LDS(k_row_r2c_crop<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_crop<IN_U8_F32>, P->ldsRowF); }
+            if (P->bzUW.L) { if (P->half) SET_LDS(k_row_c2r_bz<true>, P->ldsRowI); else SET_LDS(k_row_c2r_bz<false>, P->ldsRowI); }
+            else if (P->half) SET_LDS(k_row_c2r<true>, P->ldsRowI);
+            else SET_LDS(k_row_c2r<false>, P->ldsRowI);
+            if (P->bzH.L || P->bzUH.L) switch (P->TK) {
+            case 8: SET_LDS((k_col_crop<8, true>), P->ldsCol); break;
+            case 4: SET_LDS((k_col_crop<4, true>), P->ldsCol); break;
+            case 2: SET_LDS((k_col_crop<2, true>), P->ldsCol); break;
+            default: SET_LDS((k_col_crop<1, true>), P->ldsCol); break;
+            }
+            else switch (P->TK) {
             case 8: SET_LDS(k_col_crop<8>, P->ldsCol); break;
             case 4: SET_LDS(k_col_crop<4>, P->ldsCol); break;
             case 2: SET_LDS(k_col_crop<2>, P->ldsCol); break;
@@ -129,6 +144,19 @@ int kernels_set_attributes(fftup_plan* P)
         const bool generic = !P->tuned && !P->mixed;
         // (same predicate as launch_frame: a plan-time plan without a row factorization runs the size-generic row kernel)
         const bool generic_rows = generic || (P->mixed == 3 && P->jit->choice.row_kind == 2);
+        if (P->bz) {                                         // FFTUP_FLAG_ANY_SIZE: the kernels with a Bluestein transform this plan launches
+            if (P->bzW.L) {
+                if (P->half) { SET_LDS(k_row_r2c_bz<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_bz<IN_U8_F16>, P->ldsRowF); }
+                else { SET_LDS(k_row_r2c_bz<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_bz<IN_U8_F32>, P->ldsRowF); }
+            }
+            if (P->bzUW.L) { if (P->half) SET_LDS(k_row_c2r_bz<true>, P->ldsRowI); else SET_LDS(k_row_c2r_bz<false>, P->ldsRowI); }
+            if (P->bzH.L || P->bzUH.L) switch (P->TK) {
+            case 8: SET_LDS(k_col_bz<8>, P->ldsCol); break;
+            case 4: SET_LDS(k_col_bz<4>, P->ldsCol); break;
+            case 2: SET_LDS(k_col_bz<2>, P->ldsCol); break;
+            default: SET_LDS(k_col_bz<1>, P->ldsCol); break;
+            }
+        }
         if (generic_rows && !cplx && !P->dbl) {
             if (P->half) { SET_LDS(k_row_r2c<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c<IN_U8_F16>, P->ldsRowF); }
             else { SET_LDS(k_row_r2c<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c<IN_U8_F32>, P->ldsRowF); }
@@ -440,9 +468,18 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
     if (which < 0 || which == 0) {
         DownRowParams p{};
         p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
-        p.TK = P->TK; p.NT = P->NT; p.h = (int)P->uW / 2;
+        p.TK = P->TK; p.NT = P->NT; p.h = (int)P->uW / 2; p.bz = P->bzW;
         const dim3 grid(P->H / 2, 3), block(P->thrW);
-        if (kind == 2) {
+        if (kind == 2) { p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0; }
+        else { p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride; }
+        if (P->bzW.L) {                                      // Bluestein rows (FFTUP_FLAG_ANY_SIZE)
+            if (kind == 2) {
+                if (P->half) hipLaunchKernelGGL((k_row_r2c_crop<IN_U8_F16, true>), grid, block, P->ldsRowF, st, p);
+                else hipLaunchKernelGGL((k_row_r2c_crop<IN_U8_F32, true>), grid, block, P->ldsRowF, st, p);
+            }
+            else if (P->half) hipLaunchKernelGGL((k_row_r2c_crop<IN_F16, true>), grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL((k_row_r2c_crop<IN_F32, true>), grid, block, P->ldsRowF, st, p);
+        } else if (kind == 2) {
             p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
             if (P->half) hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
@@ -456,8 +493,15 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
         DownColParams p{};
         p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
         p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
+        p.bzH = P->bzH; p.bzUH = P->bzUH;
         const dim3 grid(P->NT, 3), block(P->thrCol);
-        switch (P->TK) {
+        if (P->bzH.L || P->bzUH.L) switch (P->TK) {          // a Bluestein column transform (FFTUP_FLAG_ANY_SIZE)
+        case 8: hipLaunchKernelGGL((k_col_crop<8, true>), grid, block, P->ldsCol, st, p); break;
+        case 4: hipLaunchKernelGGL((k_col_crop<4, true>), grid, block, P->ldsCol, st, p); break;
+        case 2: hipLaunchKernelGGL((k_col_crop<2, true>), grid, block, P->ldsCol, st, p); break;
+        default: hipLaunchKernelGGL((k_col_crop<1, true>), grid, block, P->ldsCol, st, p); break;
+        }
+        else switch (P->TK) {
         case 8: hipLaunchKernelGGL(k_col_crop<8>, grid, block, P->ldsCol, st, p); break;
         case 4: hipLaunchKernelGGL(k_col_crop<4>, grid, block, P->ldsCol, st, p); break;
         case 2: hipLaunchKernelGGL(k_col_crop<2>, grid, block, P->ldsCol, st, p); break;
@@ -471,7 +515,11 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
         p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->uW; p.uW = (int)P->uW;
         p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = 0; p.zrx = 0; p.inv_norm = 1.0f / (float)P->uW; p.poly = 0;
         const dim3 grid(P->uH / 2, 3), block(P->thrUW);
-        if (P->half) hipLaunchKernelGGL(k_row_c2r<true>, grid, block, P->ldsRowI, st, p);
+        if (P->bzUW.L) {
+            if (P->half) hipLaunchKernelGGL(k_row_c2r_bz<true>, grid, block, P->ldsRowI, st, p, P->bzUW);
+            else hipLaunchKernelGGL(k_row_c2r_bz<false>, grid, block, P->ldsRowI, st, p, P->bzUW);
+        }
+        else if (P->half) hipLaunchKernelGGL(k_row_c2r<true>, grid, block, P->ldsRowI, st, p);
         else hipLaunchKernelGGL(k_row_c2r<false>, grid, block, P->ldsRowI, st, p);
         P->R_valid = true;
     }
@@ -698,6 +746,17 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
                                      P->lanes[P->cur].stream, q));
         } else if (P->mixed == 1 || P->mixed == 2) {
             if (P->mixed == 1) launch_row_mixed<MixedCfg1080>(P, in_slot, kind); else launch_row_mixed<MixedCfg720>(P, in_slot, kind);
+        } else if (P->bzW.L) {                               // Bluestein rows (FFTUP_FLAG_ANY_SIZE)
+            hipStream_t st = P->lanes[P->cur].stream;
+            if (kind == 2) {
+                p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+                if (P->half) hipLaunchKernelGGL(k_row_r2c_bz<IN_U8_F16>, grid, block, P->ldsRowF, st, p, P->bzW);
+                else hipLaunchKernelGGL(k_row_r2c_bz<IN_U8_F32>, grid, block, P->ldsRowF, st, p, P->bzW);
+            } else {
+                p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+                if (P->half) hipLaunchKernelGGL(k_row_r2c_bz<IN_F16>, grid, block, P->ldsRowF, st, p, P->bzW);
+                else hipLaunchKernelGGL(k_row_r2c_bz<IN_F32>, grid, block, P->ldsRowF, st, p, P->bzW);
+            }
         } else if (kind == 2) {
             p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
             if (P->half) hipLaunchKernelGGL(k_row_r2c<IN_U8_F16>, grid, block, P->ldsRowF, P->lanes[P->cur].stream, p);
@@ -726,6 +785,11 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
             }
             else if (P->mixed == 1) hipLaunchKernelGGL(k_col_m<MixedCfg1080>, grid, dim3(4 * MixedCfg1080::COL_TPC), P->ldsCol, P->lanes[P->cur].stream, q);
             else hipLaunchKernelGGL(k_col_m<MixedCfg720>, grid, dim3(4 * MixedCfg720::COL_TPC), P->ldsCol, P->lanes[P->cur].stream, q);
+        } else if (P->bzH.L || P->bzUH.L) switch (P->TK) {    // a Bluestein column transform (FFTUP_FLAG_ANY_SIZE)
+        case 8: hipLaunchKernelGGL(k_col_bz<8>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p, P->bzH, P->bzUH); break;
+        case 4: hipLaunchKernelGGL(k_col_bz<4>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p, P->bzH, P->bzUH); break;
+        case 2: hipLaunchKernelGGL(k_col_bz<2>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p, P->bzH, P->bzUH); break;
+        default: hipLaunchKernelGGL(k_col_bz<1>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p, P->bzH, P->bzUH); break;
         } else if (P->poly) switch (P->TK) {
         case 8: hipLaunchKernelGGL(k_col_poly<8>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p); break;
         case 4: hipLaunchKernelGGL(k_col_poly<4>, grid, block, P->ldsCol, P->lanes[P->cur].stream, p); break;
@@ -759,6 +823,9 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
             }
             else if (P->mixed == 1) launch_c2r_ct<MixedCfg1080::CT>(P, grid, p);
             else launch_c2r_ct<MixedCfg720::CT>(P, grid, p);
+        } else if (P->bzUW.L) {                              // Bluestein rows (FFTUP_FLAG_ANY_SIZE)
+            if (P->half) hipLaunchKernelGGL(k_row_c2r_bz<true>, grid, block, P->ldsRowI, P->lanes[P->cur].stream, p, P->bzUW);
+            else hipLaunchKernelGGL(k_row_c2r_bz<false>, grid, block, P->ldsRowI, P->lanes[P->cur].stream, p, P->bzUW);
         } else if (P->half) hipLaunchKernelGGL(k_row_c2r<true>, grid, block, P->ldsRowI, P->lanes[P->cur].stream, p);
         else hipLaunchKernelGGL(k_row_c2r<false>, grid, block, P->ldsRowI, P->lanes[P->cur].stream, p);
         P->R_valid = true;

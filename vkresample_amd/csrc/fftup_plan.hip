@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <complex>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -130,6 +131,76 @@ static int make_rotations(fftup_plan* P, float2** dptr, uint32_t n)
     int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
     if (rc) return rc;
     HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
+    return FFTUP_OK;
+}
+
+// ---- FFTUP_FLAG_ANY_SIZE: lengths with a prime factor above 7 run as Bluestein transforms (kernels_bluestein.hpp)
+static constexpr uint32_t BZ_MAX_N = 4096;      // the longest such length: L = 8192 >= 2 N - 1 always exists and its buffers fit
+// do two LDS buffers of `points` complex fp32 points share the 160 KB of a gfx950 compute unit?
+static bool two_buffers_fit(size_t points) { return 2 * sizeof(float2) * (size_t)lpad_size((int)points) <= (size_t)160 * 1024; }
+// the smallest 2,3,5,7-smooth length >= 2n - 1 whose two buffers of L * tk points fit (0: none)
+static uint32_t bluestein_length(uint32_t n, int tk)
+{
+    for (uint32_t L = 2 * n - 1; two_buffers_fit((size_t)L * tk); L++)
+        if (is_smooth(L)) return L;
+    return 0;
+}
+// length of the LDS sequences the transform of n points works on with tiles of tk: n, its Bluestein length, or 0 (does not fit)
+static uint32_t lds_length(uint32_t n, int tk)
+{
+    if (!is_smooth(n)) return bluestein_length(n, tk);
+    return two_buffers_fit((size_t)n * tk) ? n : 0;
+}
+// column tile width of a plan with a Bluestein column transform: the widest of 8, 4, 2, 1 at which both column transforms fit
+// with the SMALLEST L (a wider tile beats a longer L: the row kernels read and write pieces of tk elements); 0: none
+static int bluestein_col_tk(uint32_t H, uint32_t uH)
+{
+    for (int tk : {8, 4, 2, 1})
+        if (lds_length(H, tk) && lds_length(uH, tk)) return tk;
+    return 0;
+}
+// DFT with exp(+2 pi i nk / n) of a smooth length in double (recursive decimation in time by the smallest prime factor)
+static void host_fft(std::vector<std::complex<double>>& x)
+{
+    const size_t n = x.size();
+    if (n <= 1) return;
+    size_t p = 2;
+    while (n % p) p++;
+    const size_t m = n / p;
+    std::vector<std::vector<std::complex<double>>> sub(p, std::vector<std::complex<double>>(m));
+    for (size_t j = 0; j < m; j++)
+        for (size_t r = 0; r < p; r++) sub[r][j] = x[j * p + r];
+    for (auto& v : sub) host_fft(v);
+    for (size_t k = 0; k < n; k++) {
+        std::complex<double> acc = sub[0][k % m];
+        for (size_t r = 1; r < p; r++) acc += sub[r][k % m] * std::polar(1.0, 2.0 * M_PI * (double)((r * k) % n) / (double)n);
+        x[k] = acc;
+    }
+}
+// the tables of one Bluestein transform of n points through length L, in double, rounded once to fp32 (as make_twiddles).  The
+// phase pi k^2 / n is reduced as (k^2 mod 2n) in 64-bit integers BEFORE the division: it reaches thousands of radians.
+static int make_bluestein(fftup_plan* P, BzPlan* z, uint32_t n, uint32_t L, const StagePlan& planL)
+{
+    std::vector<std::complex<double>> w(n), b(L, std::complex<double>(0.0, 0.0));
+    for (uint64_t k = 0; k < n; k++) w[k] = std::polar(1.0, M_PI * (double)((k * k) % (2 * (uint64_t)n)) / (double)n);
+    for (uint32_t k = 0; k < n; k++) {
+        b[k] = std::conj(w[k]);
+        if (k) b[L - k] = std::conj(w[k]);           // (L >= 2n - 1: the two wings do not meet)
+    }
+    host_fft(b);
+    std::vector<float2> hc(n), hb(L);
+    for (uint32_t k = 0; k < n; k++) hc[k] = make_float2((float)w[k].real(), (float)w[k].imag());
+    for (uint32_t k = 0; k < L; k++) hb[k] = make_float2((float)(b[k].real() / (double)L), (float)(b[k].imag() / (double)L));
+    float2 *dc = nullptr, *db = nullptr, *dt = nullptr;
+    int rc = dev_alloc(P, (void**)&dc, sizeof(float2) * n);
+    if (rc) return rc;
+    rc = dev_alloc(P, (void**)&db, sizeof(float2) * L);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(dc, hc.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(db, hb.data(), sizeof(float2) * L, hipMemcpyHostToDevice));
+    rc = make_twiddles(P, &dt, L);
+    if (rc) return rc;
+    z->L = (int32_t)L; z->plan = planL; z->tw = dt; z->chirp = dc; z->bhat = db;
     return FFTUP_OK;
 }
 
@@ -347,8 +418,24 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         return fail(FFTUP_E_INVALID_ARG, "width/height (and upscaled sizes) must be even, upscale >= 1");
     if (down && (uW < 2 || uH < 2 || uW >= W || uH >= H))
         return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the output sizes must be at least 2 and below the input's");
-    if (!is_smooth(W) || !is_smooth(H) || !is_smooth(uW) || !is_smooth(uH))
-        return fail(FFTUP_E_UNSUPPORTED_SIZE, "sizes must factor into 2,3,5,7 (vkFFT.h:4719-4726)");
+    // FFTUP_FLAG_ANY_SIZE: lengths with a prime factor above 7 run as Bluestein transforms; `bz`: this plan has one.  A plan
+    // whose four lengths are smooth is the same plan with or without the flag.
+    const bool bz = !is_smooth(W) || !is_smooth(H) || !is_smooth(uW) || !is_smooth(uH);
+    if (bz && !(cfg->flags & FFTUP_FLAG_ANY_SIZE))
+        return fail(FFTUP_E_UNSUPPORTED_SIZE, "sizes must factor into 2,3,5,7 (vkFFT.h:4719-4726); FFTUP_FLAG_ANY_SIZE accepts any even length up to 4096");
+    if (bz) {
+        // (arithmetic on the sizes, before any device access)
+        if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need sizes that factor into 2,3,5,7 (FFTUP_FLAG_ANY_SIZE covers the FFT modes only)");
+        if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_ANY_SIZE plans with a non-smooth length exist for -p 0 and -p 2");
+        for (uint32_t n : {W, H, uW, uH})
+            if (!is_smooth(n) && n > BZ_MAX_N)
+                return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: " + std::to_string(n) + " has a prime factor above 7 and is longer than 4096");
+        // the smooth lengths of such a plan keep their Stockham transforms in the same kernels: two-buffer R2C rows, columns in LDS
+        if (W > 8192u || uW > 8192u)
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: a plan with a non-smooth length needs rows of at most 8192 points (no non-R2C or four-step path)");
+        if (!bluestein_col_tk(H, uH))
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: a plan with a non-smooth length needs columns that fit the LDS (no four-step columns)");
+    }
     // R2C rule of the reference: uW <= maxComputeSharedMemorySize/8 with 64 KB (VkResample.cpp:1424; complexSizeCalc = 16
     // for -p 1, VkResample.cpp:1334-1336, halves the limit); beyond it the full complex path runs
     const bool cplx = uW > (cfg->precision == 1 ? 4096u : 8192u);
@@ -392,6 +479,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     P->cplx = cplx;
     P->dct = dct;
     P->down = down;
+    P->bz = bz;
     // (FFT downscale plans keep only the bins the output holds, kx <= uW/2: S1, S2 and the column pass shrink with the output)
     P->ncols = cplx ? (int)W : (down && !dct) ? (int)(uW / 2 + 1) : (int)(W / 2 + 1);
     P->esz = P->dbl ? 8 : (P->half ? 2 : 4);
@@ -447,7 +535,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             // u = 2 with the symmetric guard: the polyphase column kernel (k_col_poly: forward, phase, length-H inverse in ONE buffer of
             // H TK points, odd rows out; the C2R kernel takes the even rows from S1) where its stages run in place
             const char* const poly_e = fftup_jit::experiment("generic_poly");
-            if (!cplx && !dct && !down && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
+            if (!cplx && !dct && !down && is_smooth(H) && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
                 for (int tk : {8, 4, 2, 1}) {
                     const size_t need = P->csz * (size_t)lpad_size((int)H * tk);
                     const int thr = inplace_threads(P->planH, tk, COL_INPLACE_PT, kernels_generic_max_threads(P->dbl));
@@ -464,6 +552,12 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                                     need <= lds_max / 2 && (size_t)(H / 2) * tk <= (size_t)COL_INPLACE_PT * thr;  // (two workgroups per compute unit)
                     if (ok) { P->TK = tk; P->ldsCol = need; P->inplaceC = true; P->thrCol = thr; break; }
                 }
+            }
+            // a Bluestein column transform: buffers of L * TK points (bluestein_col_tk: checked before any device access)
+            if (!P->TK && (!is_smooth(H) || !is_smooth(uH))) {
+                P->TK = bluestein_col_tk(H, uH);
+                P->ldsCol = 2 * P->csz * (size_t)lpad_size((int)(std::max(std::max(H, uH), std::max(lds_length(H, P->TK), lds_length(uH, P->TK))) * (uint32_t)P->TK));
+                if (P->ldsCol > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: this device's LDS does not hold the column transform"); goto bad; }
             }
             // column tile width: widest of 8,4,2,1 whose ping-pong buffers fit in LDS (downscale plans: the forward transform,
             // length H, is the longer one)
@@ -494,7 +588,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         if (P->mixed) { P->TK = 4; P->ldsCol = sizeof(float2) * (size_t)H * 4; }             // k_col_m: one in-place buffer
         // any other size with an integer or half-integer upscale factor: kernels specialised for it now (the counterpart
         // of VkFFT generating its shaders at plan time)
-        if (!P->dbl && !cplx && !dct && !down && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
+        if (!P->dbl && !cplx && !dct && !down && !bz && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
             int DD = 1;
             const int D = jit_factor(cfg->upscale, W, H, uW, uH, P->zly, P->zry, &DD);
             if (D) {
@@ -520,6 +614,11 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         P->NT = (P->ncols + P->TK - 1) / P->TK;
         P->ldsRowF = 2 * P->csz * (size_t)lpad_size((int)W);
         P->ldsRowI = 2 * P->csz * (size_t)lpad_size((int)uW);
+        if (bz) {                                            // Bluestein rows: buffers of L points
+            P->ldsRowF = 2 * P->csz * (size_t)lpad_size((int)lds_length(W, 1));
+            P->ldsRowI = 2 * P->csz * (size_t)lpad_size((int)lds_length(uW, 1));
+            if (P->ldsRowF > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: this device's LDS does not hold the row transform"); goto bad; }
+        }
         if (cplx) {                                          // long non-R2C rows: one buffer, in place (rows_fit above)
             P->inplaceF = rows_fit(W) == 1; P->inplaceI = rows_fit(uW) == 1;
             if (P->inplaceF) P->ldsRowF /= 2;
@@ -541,6 +640,11 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             P->thrW = std::min(tmax, std::max(64, round_up((int)W / 8, 64)));
             P->thrUW = std::min(tmax, std::max(64, round_up((int)uW / 8, 64)));
             if (!(P->poly || P->inplaceC)) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(H, uH) * P->TK / 8, 64)));     // (in-place column plans chose theirs above)
+            if (bz) {                                        // one thread per eight points of the sequences in LDS, as above
+                P->thrW = std::min(tmax, std::max(64, round_up((int)lds_length(W, 1) / 8, 64)));
+                P->thrUW = std::min(tmax, std::max(64, round_up((int)lds_length(uW, 1) / 8, 64)));
+                if (!P->poly) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(lds_length(H, P->TK), lds_length(uH, P->TK)) * P->TK / 8, 64)));
+            }
             // -p 1 R2C rows: one LDS buffer where every stage runs in place with 8 points per thread (two workgroups per compute unit)
             if (P->dbl && !cplx) {
                 const int tf = inplace_threads(P->planW, 1, 8, tmax), ti = inplace_threads(P->planUW, 1, 8, tmax);
@@ -558,6 +662,14 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         PLAN_RC(make_twiddles(P, &P->twUH, uH));
         for (fftup_plan::Four* f : {&P->fourF, &P->fourI, &P->colF, &P->colI})
             if (f->on) { PLAN_RC(make_twiddles(P, &f->tw1, (uint32_t)f->n1)); PLAN_RC(make_twiddles(P, &f->tw2, (uint32_t)f->n2)); }
+        if (bz) {
+            const std::pair<BzPlan*, uint32_t> axes[4] = {{&P->bzW, W}, {&P->bzH, H}, {&P->bzUW, uW}, {&P->bzUH, uH}};
+            for (int i = 0; i < 4; i++)
+                if (!is_smooth(axes[i].second)) {
+                    const uint32_t L = lds_length(axes[i].second, (i & 1) ? P->TK : 1);
+                    PLAN_RC(make_bluestein(P, axes[i].first, axes[i].second, L, make_stage_plan(L)));
+                }
+        }
         if (dct) {
             PLAN_RC(make_rotations(P, &P->rotW, W));
             PLAN_RC(make_rotations(P, &P->rotH, H));
@@ -644,6 +756,17 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
         if (f.on) s += std::string("; ") + what + " in four steps " + std::to_string(f.n1) + "*" + std::to_string(f.n2) + " (tiles of " + std::to_string(f.tka) + " / " + std::to_string(f.tkb) + ")";
     };
     four("forward rows", P->fourF); four("inverse rows", P->fourI); four("forward columns", P->colF); four("inverse columns", P->colI);
+    if (P->bz) {
+        // the Bluestein axes and their lengths L (forward / inverse; "-": that transform is a direct one)
+        auto axis = [&](const char* what, uint32_t n, uint32_t un, const BzPlan& f, const BzPlan& i) {
+            if (!f.L && !i.L) return;
+            s += std::string("; ") + what + " " + std::to_string(n) + "->" + std::to_string(un) + " bluestein L=" + (f.L ? std::to_string(f.L) : std::string("-")) + "/"
+                 + (i.L ? std::to_string(i.L) : std::string("-"));
+        };
+        axis("rows", P->W, P->uW, P->bzW, P->bzUW);
+        axis("columns", P->H, P->uH, P->bzH, P->bzUH);
+        s += "; column tiles of " + std::to_string(P->TK);
+    }
     if (P->u8out) s += "; fused 8-bit RGB store";
     snprintf(buf, buflen, "%s", s.c_str());
     return FFTUP_OK;
@@ -700,6 +823,10 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : P->down ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
     snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
+    // kernels with a Bluestein transform (kernels_bluestein.hpp)
+    const bool kbz[3] = {P->bzW.L != 0, P->bzH.L != 0 || P->bzUH.L != 0, P->bzUW.L != 0};
+    for (int i = 0; i < 3; i++)
+        if (kbz[i]) strncat(info->kernel_names[i], "_bz", 63 - strlen(info->kernel_names[i]));
     return FFTUP_OK;
 }
 

@@ -10,11 +10,14 @@
 // the output width.  For a real row the folded Nyquist bin X[h] + X[W-h] = 2 Re X[h] is real: it is stored as (2 Re A, 0) and
 // (2 Re B, 0) for the row pair, and the C2R kernel's two writes of a[uW/2] (k = uW/2 and uW - k) then agree.  fp32 arithmetic;
 // -p 2 stores R as binary16 (k_row_c2r<true>).
+// FFTUP_FLAG_ANY_SIZE: the BZ instantiations run each transform whose length is not smooth as a Bluestein transform
+// (kernels_bluestein.hpp, chosen per transform by the BzPlan members of the parameters); their LDS buffers are sized by L * TK.
 #pragma once
 #include <hip/hip_fp16.h>
 #include <hip/hip_runtime.h>
 
 #include "fft_engine.hpp"
+#include "kernels_bluestein.hpp"
 #include "kernels_generic.hpp"
 
 namespace fftup {
@@ -28,22 +31,25 @@ struct DownRowParams {
     long in_row_stride, in_plane_stride;
     int TK, NT;              // tile width (complex), number of tiles = ceil((h + 1) / TK)
     int h;                   // uW / 2: the last bin kept (folded)
+    BzPlan bz;               // BZ instantiations: the rows' Bluestein transform
 };
 
-// grid (H/2, 3); dynamic LDS = 2 * lpad_size(W) complex.  Rows 2j (real part) and 2j+1 (imaginary part).
-template <int MODE>
+// grid (H/2, 3); dynamic LDS = 2 * lpad_size(W) complex (BZ: of bz.L).  Rows 2j (real part) and 2j+1 (imaginary part).
+template <int MODE, bool BZ = false>
 __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_r2c_crop(DownRowParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* a = (float2*)smem;
-    float2* b = a + lpad_size(p.W);
+    float2* b = a + lpad_size(BZ ? p.bz.L : p.W);
     const int tid = threadIdx.x, T = blockDim.x;
     const int j = blockIdx.x, c = blockIdx.y;
     const int W = p.W, h = p.h;
     for (int n = tid; n < W; n += T)
         a[lpad(n)] = make_float2((float)load_px<MODE>(p, c, 2 * j, n), (float)load_px<MODE>(p, c, 2 * j + 1, n));
     __syncthreads();
-    const float2* Z = fft_lds<+1, 1>(a, b, p.plan, p.tw, tid, T);
+    const float2* Z;
+    if constexpr (BZ) Z = fft_bluestein<+1, 1>(a, b, W, p.bz, tid, T);
+    else Z = fft_lds<+1, 1>(a, b, p.plan, p.tw, tid, T);
     // unpack as k_row_r2c: A = (Z[k] + conj Z[W-k]) / 2, B = (Z[k] - conj Z[W-k]) / 2i; at k = h: 2 Re A, 2 Re B (h < W/2)
     const long tile_stride = (long)p.H * p.TK;
     float2* base = p.S1 + (long)c * p.NT * tile_stride;
@@ -73,15 +79,16 @@ struct DownColParams {
     int NT;
     int ncols;               // kx columns present: uW/2 + 1
     float inv_norm;          // 1/uH
+    BzPlan bzH, bzUH;        // BZ instantiations: per transform, L = 0 for a smooth length
 };
 
-// grid (NT, 3); dynamic LDS = 2 * lpad_size(H*TK) complex (the forward transform is the longer one)
-template <int TK>
+// grid (NT, 3); dynamic LDS = 2 * lpad_size(H*TK) complex (the forward transform is the longer one; BZ: max(H, bzH.L, bzUH.L) * TK)
+template <int TK, bool BZ = false>
 __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_crop(DownColParams p)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float2* a = (float2*)smem;
-    float2* b = a + lpad_size(p.H * TK);
+    float2* b = a + lpad_size((BZ ? max(p.H, max(p.bzH.L, p.bzUH.L)) : p.H) * TK);
     const int tid = threadIdx.x, T = blockDim.x;
     const int tile = blockIdx.x, c = blockIdx.y;
     const int H = p.H, uH = p.uH, hh = p.uH / 2;
@@ -93,7 +100,9 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_crop(D
         a[lpad(e)] = v;
     }
     __syncthreads();
-    float2* F = fft_lds<+1, TK>(a, b, p.planH, p.twH, tid, T);
+    float2* F;
+    if constexpr (BZ) F = fft_any<+1, TK>(a, b, p.planH, p.twH, p.bzH, tid, T);
+    else F = fft_lds<+1, TK>(a, b, p.planH, p.twH, tid, T);
     float2* G = (F == a) ? b : a;
     // crop: rows below hh as they are, row hh = F[hh] + F[H - hh], rows above hh from uH - H rows further on
     for (int e = tid; e < uH * TK; e += T) {
@@ -105,7 +114,9 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_crop(D
         G[lpad(e)] = v;
     }
     __syncthreads();
-    const float2* D = fft_lds<-1, TK>(G, F, p.planUH, p.twUH, tid, T);
+    const float2* D;
+    if constexpr (BZ) D = fft_any<-1, TK>(G, F, p.planUH, p.twUH, p.bzUH, tid, T);
+    else D = fft_lds<-1, TK>(G, F, p.planUH, p.twUH, tid, T);
     float2* dst = p.S2 + ((long)c * p.NT + tile) * uH * TK;
     for (int e = tid; e < uH * TK; e += T)
         if ((e % TK) < ncol_valid) dst[e] = cscale(D[lpad(e)], p.inv_norm);

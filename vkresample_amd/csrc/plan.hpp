@@ -18,11 +18,13 @@
 #include <vector>
 
 #include "../../include/fftup.h"
+#include "bluestein_plan.hpp"
 #include "fft_engine.hpp"
 #include "jit.hpp"
 #include "png_params.hpp"
 
 using fftup::StagePlan;
+using fftup::BzPlan;
 using fftup::PngParams;
 
 static constexpr int TUNED_TK = 4;     // column tile width of the size-specialised kernels
@@ -90,6 +92,10 @@ struct fftup_plan {
                   StagePlan p1{}, p2{}; float2 *tw1 = nullptr, *tw2 = nullptr; size_t ldsA = 0, ldsB = 0; int thrA = 64, thrB = 64; };
     Four fourF, fourI;
     Four colF, colI;                  // columns longer than the LDS (TK = 1): the same two kernels on dense columns
+    // FFTUP_FLAG_ANY_SIZE: per transform, L != 0 = the length has a prime factor above 7 and runs as a Bluestein transform of
+    // length L (kernels_bluestein.hpp); `bz`: the plan has at least one such transform (size-generic R2C kernels, fp32 arithmetic)
+    BzPlan bzW{}, bzH{}, bzUW{}, bzUH{};
+    bool bz = false;
     int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
     int pairs_per_strip = 6;
     bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
