@@ -30,7 +30,7 @@ extern "C" {
 /* ---- error codes (reference: VkResult ints, 0 = VK_SUCCESS; VR:1286-1320, 1364-1367) ---- */
 enum {
     FFTUP_OK = 0,
-    FFTUP_E_INVALID_ARG = 1,    /* null pointer, bad slot, odd size, channels != 3 (VR:1368)            */
+    FFTUP_E_INVALID_ARG = 1,    /* null pointer, bad slot, odd size (without FFTUP_FLAG_ODD_SIZE), channels != 3 (VR:1368) */
     FFTUP_E_UNSUPPORTED_SIZE = 2, /* a dimension is not 2,3,5,7-smooth: VF:4719-4726
                                      (VK_ERROR_FORMAT_NOT_SUPPORTED); with FFTUP_FLAG_ANY_SIZE: such a
                                      dimension is longer than 4096, or the plan is outside that flag's
@@ -105,7 +105,7 @@ enum {
                                         _GENERIC_KERNELS, _UNFUSED_SHARPEN and _TUNE_PLAN are accepted and change nothing).
                                         Accepted: -p 0 and -p 2 (-p 1: FFTUP_E_UNSUPPORTED_PRECISION), W <= 8192 and columns whose
                                         transforms fit the compute unit's local memory: FFTUP_E_UNSUPPORTED_SIZE otherwise       */
-    FFTUP_FLAG_ANY_SIZE = 1024u      /* EXTENSION: widens the set of accepted SIZES and changes nothing else.  Without the flag: the
+    FFTUP_FLAG_ANY_SIZE = 1024u,     /* EXTENSION: widens the set of accepted SIZES and changes nothing else.  Without the flag: the
                                         reference's rule, every length (W, H, uW, uH) 2,3,5,7-smooth.  With it, on a plan whose four
                                         lengths are smooth: a no-op -- same kernels (ahead-of-time and plan-time ones included), same
                                         fftup_info, same output bytes.  Otherwise: the lengths still have to be even and at least 2
@@ -128,12 +128,46 @@ enum {
                                         decided before any device access.  fftup_jit_check keeps returning FFTUP_E_UNSUPPORTED_SIZE
                                         for these sizes, and fftup_version() is unchanged: detect the mode by creating a plan -- a
                                         library without it returns FFTUP_E_UNSUPPORTED_SIZE for 46x22 with the flag set         */
+    FFTUP_FLAG_ODD_SIZE = 2048u      /* EXTENSION: accepts odd widths and heights, input or output, and changes nothing else.
+                                        Without the flag: an odd W, H, uW or uH is FFTUP_E_INVALID_ARG, as before (also with
+                                        FFTUP_FLAG_ANY_SIZE alone).  With it, on a plan whose four lengths are even: a no-op -- same
+                                        kernels (ahead-of-time and plan-time ones included), same fftup_info, same output bytes.
+                                        With it and at least one of W, H, uW, uH odd: sizes follow the usual rule
+                                        uW = (uint32_t)(u W), uH = (uint32_t)(u H) in fp32, each length at least 2, and the plan
+                                        computes EXACT TRIGONOMETRIC RESAMPLING per axis, separably (scipy.signal.resample's rule,
+                                        the one FFTUP_FLAG_DOWNSCALE names).  Per axis, input x[n], n < N, output length M,
+                                        X = DFT_N(x), K = min(N, M): the bins |k| < K/2 are copied, Y[k mod M] = X[k mod N]; if K
+                                        is even its Nyquist bin h = K/2 is split for M > N, Y[h] = Y[M-h] = X[h]/2, folded for
+                                        M < N, Y[h] = X[h] + X[N-h] (FFTUP_FLAG_DOWNSCALE's rule, unchanged), kept for M = N; every
+                                        other bin of Y is 0.  The pre-sharpen image is R = 1/(uW uH) IDFT(Y) over both axes, the
+                                        amplitude-preserving image y = R (uW uH) / (W H): constants stay constant, -u 1 reproduces
+                                        the input, output pixel m sits at input position m N / M.  The quirks B1-B3 of the
+                                        reference's even-size path do NOT apply on either axis of such a plan (an even axis beside
+                                        an odd one included).  The sharpen pass is the existing one, unchanged (upsq = "%f"(u u),
+                                        quirks B4 and B5).  A 2,3,5,7-smooth odd length runs the Stockham stages; a length with a
+                                        prime factor above 7, odd or even, needs FFTUP_FLAG_ANY_SIZE as well, must be at most 4096
+                                        and runs as a Bluestein transform (without that flag, or above 4096:
+                                        FFTUP_E_UNSUPPORTED_SIZE).  With FFTUP_FLAG_DOWNSCALE (FFT mode): factors in [0.125, 1),
+                                        output lengths below the input's.  Bounds as for Bluestein plans: -p 0 and -p 2 (-p 1:
+                                        FFTUP_E_UNSUPPORTED_PRECISION), rows of at most 8192 points, columns whose transforms fit
+                                        the compute unit's local memory (no non-R2C or four-step path: FFTUP_E_UNSUPPORTED_SIZE);
+                                        with FFTUP_FLAG_DCT an odd length is FFTUP_E_UNSUPPORTED_SIZE.  Such a plan runs four
+                                        launches of size-generic kernels (fftup_info.tuned = u8_store = 0, the three transform
+                                        kernels' names carry "_odd", and "_bz" behind it where a Bluestein transform runs);
+                                        FFTUP_FLAG_FUSE_U8_STORE, _GENERIC_KERNELS, _UNFUSED_SHARPEN and _TUNE_PLAN are accepted and
+                                        change nothing; FFTUP_FLAG_FUSE_U8_LOAD and every execution path work as on other plans.
+                                        fftup_output_checksum of binary16 planes with uW uH odd: the two bytes behind the last
+                                        whole word enter the sum as one more word, zero-extended.  All of this is arithmetic on the
+                                        sizes, decided before any device access.  fftup_jit_check keeps returning
+                                        FFTUP_E_UNSUPPORTED_SIZE for these sizes, and fftup_version() is unchanged: detect the mode
+                                        by creating a plan -- a library without it returns FFTUP_E_INVALID_ARG for 45x21 -u 2 with
+                                        the flag set                                                                            */
 };
 
 /* Replaces VkResampleConfiguration (VR:45-59) + the part of VkFFTConfiguration (VF:22-94) that
  * launchResample() derives from it (VR:1409-1503). */
 typedef struct fftup_config {
-    uint32_t width, height;   /* input image size; both even                                         */
+    uint32_t width, height;   /* input image size; both even (odd: FFTUP_FLAG_ODD_SIZE)                */
     uint32_t channels;        /* must be 3 (stbi_load(...,3) VR:1362, channels = 3 VR:1368)           */
     float    upscale;         /* -u; output = (uint32_t)(upscale*size) (VR:1417-1418)                */
     uint32_t precision;       /* -p: 0 single, 1 double (VR:1422), 2 half-memory/fp32-math (VR:1420-1421) */
@@ -190,7 +224,8 @@ FFTUP_API int fftup_device_pci_bus_id(int device, char* buf, size_t buflen);
  * non-R2C path (VR:1424); rows and columns too long for the compute unit's local memory run as two-launch "four-step"
  * transforms through device memory (the reference's multi-upload plans, VF:4773-4992).  fftup_plan_describe says which.
  * FFTUP_FLAG_DCT plans accept a subset of these sizes (see the flag); FFTUP_FLAG_DOWNSCALE plans take factors below 1;
- * FFTUP_FLAG_ANY_SIZE lifts the smoothness rule for even lengths up to 4096 (Bluestein transforms, see the flag). */
+ * FFTUP_FLAG_ANY_SIZE lifts the smoothness rule for even lengths up to 4096 (Bluestein transforms, see the flag);
+ * FFTUP_FLAG_ODD_SIZE accepts odd lengths (exact trigonometric resampling, see the flag). */
 FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);

@@ -19,6 +19,7 @@ FLAG_OVERLAP_ITERATIONS = 128
 FLAG_DCT = 256                    # DCT-II -> zero-pad -> DCT-III instead of the periodic FFT (library 0.7.0 on)
 FLAG_DOWNSCALE = 512              # upscale in [1/8, 1): spectrum cropped (older libraries refuse such plans: FFTUP_E_INVALID_ARG)
 FLAG_ANY_SIZE = 1024              # even lengths with a prime factor above 7, up to 4096: Bluestein transforms (older libraries: FFTUP_E_UNSUPPORTED_SIZE)
+FLAG_ODD_SIZE = 2048              # odd widths and heights: exact trigonometric resampling per axis (older libraries: FFTUP_E_INVALID_ARG)
 
 # every symbol include/fftup.h declares
 EXPORTS = [

@@ -44,7 +44,8 @@ def device_pci_bus_id(device=0):
 
 class Upscaler:
     """One plan = one (width, height, upscale, precision, sharpen, device) configuration.  `flags`: the FLAG_* bits of _lib
-    (include/fftup.h), e.g. FLAG_ANY_SIZE (1024) for even sizes that do not factor into 2,3,5,7."""
+    (include/fftup.h), e.g. FLAG_ANY_SIZE (1024) for even sizes that do not factor into 2,3,5,7, FLAG_ODD_SIZE (2048) for odd widths
+    and heights."""
 
     def __init__(self, width, height, upscale=2.0, precision=0, sharpen=0.2, device=0, flags=0, ring=1):
         self._lib = _lib.load()

@@ -17,6 +17,7 @@
 //                 default keeps them in order like the reference's barriers, VR:1217, vkFFT.h:7678)
 //   -dct          FFTUP_FLAG_DCT: DCT-II -> zero-pad -> DCT-III instead of the periodic FFT (no wrap-around ringing at the borders)
 //   -anysize      FFTUP_FLAG_ANY_SIZE: even sizes with a prime factor above 7 (up to 4096 per such length) run as Bluestein transforms
+//   -oddsize      FFTUP_FLAG_ODD_SIZE: odd widths and heights, input or output (exact trigonometric resampling per axis)
 //   -downscale    FFTUP_FLAG_DOWNSCALE: -u in [1/8, 1) crops the spectrum (band-limited decimation; with -dct: truncated DCT)
 #include <algorithm>
 #include <atomic>
@@ -189,8 +190,10 @@ static int launchResample(ResampleConfiguration config)                      // 
     if (res != FFTUP_OK) {
         // (the hint is appended: the message of the code stays as it is)
         const bool hint = res == FFTUP_E_UNSUPPORTED_SIZE && !(config.flags & FFTUP_FLAG_ANY_SIZE);
-        printf("Plan creation failed: %s (%s)%s\n", fftup_strerror(res), fftup_last_error(),
-               hint ? "; -anysize accepts even sizes with larger prime factors (each such length up to 4096)" : "");
+        const bool odd_hint = res == FFTUP_E_INVALID_ARG && !(config.flags & FFTUP_FLAG_ODD_SIZE) && strstr(fftup_last_error(), "must be even");
+        printf("Plan creation failed: %s (%s)%s%s\n", fftup_strerror(res), fftup_last_error(),
+               hint ? "; -anysize accepts even sizes with larger prime factors (each such length up to 4096)" : "",
+               odd_hint ? "; -oddsize accepts odd widths and heights" : "");
         return res;
     }
     if (config.threadId == 0) {
@@ -345,6 +348,7 @@ int main(int argc, char* argv[])
         printf("	-overlap: the -n iterations overlap on several streams: 'Time:' becomes a throughput figure, not the original's serial one\n");
         printf("	-dct: DCT upscale instead of FFT: the image is not treated as periodic, no ringing at the borders (-p 0 and -p 2)\n");
         printf("	-anysize: accept even sizes that do not factor into 2,3,5,7 (each such length up to 4096; Bluestein transforms; -p 0 and -p 2, not with -dct)\n");
+        printf("	-oddsize: accept odd widths and heights, e.g. 853x480 or -u 1.5 on 62x38: exact trigonometric resampling (-p 0 and -p 2, not with -dct; with -anysize: any length up to 4096)\n");
         printf("	-downscale: allow -u in [1/8, 1), e.g. -u 1/2: spectral downscale (band-limited, no aliasing; -p 0 and -p 2; with -dct: DCT downscale)\n");
         return 0;
     }
@@ -389,6 +393,7 @@ int main(int argc, char* argv[])
     if (findFlag(B, E, "-overlap")) config.flags |= FFTUP_FLAG_OVERLAP_ITERATIONS;
     if (findFlag(B, E, "-dct")) config.flags |= FFTUP_FLAG_DCT;
     if (findFlag(B, E, "-anysize")) config.flags |= FFTUP_FLAG_ANY_SIZE;
+    if (findFlag(B, E, "-oddsize")) config.flags |= FFTUP_FLAG_ODD_SIZE;
     if (findFlag(B, E, "-downscale")) config.flags |= FFTUP_FLAG_DOWNSCALE;
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");

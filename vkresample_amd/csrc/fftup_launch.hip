@@ -19,6 +19,7 @@
 #include "kernels_dct.hpp"
 #include "kernels_downscale.hpp"
 #include "kernels_bluestein.hpp"
+#include "kernels_odd.hpp"
 
 using namespace fftup;
 
@@ -113,6 +114,17 @@ int kernels_set_attributes(fftup_plan* P)
             case 4: SET_LDS(k_dct_col<4>, P->ldsCol); break;
             case 2: SET_LDS(k_dct_col<2>, P->ldsCol); break;
             default: SET_LDS(k_dct_col<1>, P->ldsCol); break;
+            }
+            return FFTUP_OK;
+        }
+        if (P->odd) {                                        // (FFTUP_FLAG_ODD_SIZE: the odd-size plan's kernels only, kernels_odd.hpp)
+            if (P->half) { SET_LDS(k_row_r2c_odd<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_odd<IN_U8_F16>, P->ldsRowF); SET_LDS(k_row_c2r_odd<true>, P->ldsRowI); }
+            else { SET_LDS(k_row_r2c_odd<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_odd<IN_U8_F32>, P->ldsRowF); SET_LDS(k_row_c2r_odd<false>, P->ldsRowI); }
+            switch (P->TK) {
+            case 8: SET_LDS(k_col_odd<8>, P->ldsCol); break;
+            case 4: SET_LDS(k_col_odd<4>, P->ldsCol); break;
+            case 2: SET_LDS(k_col_odd<2>, P->ldsCol); break;
+            default: SET_LDS(k_col_odd<1>, P->ldsCol); break;
             }
             return FFTUP_OK;
         }
@@ -529,6 +541,57 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
     return FFTUP_OK;
 }
 
+// FFTUP_FLAG_ODD_SIZE with an odd length: row R2C keeping kx <= min(W, uW)/2 -> column forward / bin map / inverse -> row C2R ->
+// sharpen (kernels_odd.hpp).  Up, down or -u 1; (rows + 1) / 2 workgroups per plane, the last one with a single row when odd.
+static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+{
+    hipStream_t st = P->lanes[P->cur].stream;
+    const int kind = P->in_kind[in_slot];
+    const int kmax = (int)std::min(P->W, P->uW) / 2;
+    if (which < 0 || which == 0) {
+        OddRowParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        p.TK = P->TK; p.NT = P->NT; p.kmax = kmax; p.fold = (P->uW < P->W && !(P->uW & 1)) ? 1 : 0; p.bz = P->bzW;
+        const dim3 grid((P->H + 1) / 2, 3), block(P->thrW);
+        if (kind == 2) {
+            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
+        } else {
+            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_odd<IN_F32>, grid, block, P->ldsRowF, st, p);
+        }
+    }
+    if (which < 0 || which == 1) {
+        OddColParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
+        p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
+        p.bzH = P->bzH; p.bzUH = P->bzUH;
+        const dim3 grid(P->NT, 3), block(P->thrCol);
+        switch (P->TK) {
+        case 8: hipLaunchKernelGGL(k_col_odd<8>, grid, block, P->ldsCol, st, p); break;
+        case 4: hipLaunchKernelGGL(k_col_odd<4>, grid, block, P->ldsCol, st, p); break;
+        case 2: hipLaunchKernelGGL(k_col_odd<2>, grid, block, P->ldsCol, st, p); break;
+        default: hipLaunchKernelGGL(k_col_odd<1>, grid, block, P->ldsCol, st, p); break;
+        }
+    }
+    if (which < 0 || which == 2) {
+        OddC2RParams p{};
+        p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.uW = (int)P->uW; p.uH = (int)P->uH;
+        p.TK = P->TK; p.NT = P->NT; p.kmax = kmax; p.halve = (P->uW > P->W && !(P->W & 1)) ? 1 : 0; p.inv_norm = 1.0f / (float)P->uW;
+        p.bz = P->bzUW;
+        const dim3 grid((P->uH + 1) / 2, 3), block(P->thrUW);
+        if (P->half) hipLaunchKernelGGL(k_row_c2r_odd<true>, grid, block, P->ldsRowI, st, p);
+        else hipLaunchKernelGGL(k_row_c2r_odd<false>, grid, block, P->ldsRowI, st, p);
+        P->R_valid = true;
+    }
+    if (which < 0 || which == 3) launch_sharpen(P, out_slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FFTUP_OK;
+}
+
 // -p 1: the size-generic kernels instantiated on double2 + the double sharpen
 static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
@@ -723,6 +786,7 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
     if (P->cplx) return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
     if (P->dbl) return launch_frame_f64(P, in_slot, out_slot, which);
     if (P->dct) return launch_frame_dct(P, in_slot, out_slot, which);
+    if (P->odd) return launch_frame_odd(P, in_slot, out_slot, which);
     if (P->down) return launch_frame_down(P, in_slot, out_slot, which);
     if (P->tuned) {
         launch_frame_tuned(P, in_slot, out_slot, which);
@@ -853,8 +917,11 @@ __global__ void __launch_bounds__(256) k_checksum(const uint32_t* __restrict__ w
 
 void launch_checksum(fftup_plan* P, uint32_t slot, hipStream_t st)
 {
-    const size_t nwords = (size_t)3 * P->uW * P->uH * (P->u8out ? 1 : P->esz) / 4;       // (uW, uH even: whole words for binary16 and bytes too)
+    const size_t nbytes = (size_t)3 * P->uW * P->uH * (P->u8out ? 1 : P->esz), nwords = nbytes / 4;   // (uW, uH even: whole words for binary16 and bytes too)
     hipLaunchKernelGGL(k_checksum, dim3(1024), dim3(256), 0, st, (const uint32_t*)P->out[slot], nwords, (unsigned long long*)P->d_sum);
+    // (FFTUP_FLAG_ODD_SIZE, binary16 planes with uW uH odd: two bytes are left over -- one more word, zero-extended)
+    if (nbytes & 3)
+        hipLaunchKernelGGL(k_checksum_tail, dim3(1), dim3(64), 0, st, (const uint8_t*)P->out[slot] + 4 * nwords, (int)(nbytes & 3), (unsigned long long*)P->d_sum);
 }
 
 #ifdef FFTUP_PLANE_STAMPS

@@ -414,8 +414,12 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     if (!(cfg->sharpen == cfg->sharpen)) return fail(FFTUP_E_INVALID_ARG, "sharpen is NaN");
     const uint32_t uW = (uint32_t)(cfg->upscale * (float)W);     // VkResample.cpp:1417-1418
     const uint32_t uH = (uint32_t)(cfg->upscale * (float)H);
-    if (W < 2 || H < 2 || (W & 1) || (H & 1) || (uW & 1) || (uH & 1) || (!down && (uW < W || uH < H)))
-        return fail(FFTUP_E_INVALID_ARG, "width/height (and upscaled sizes) must be even, upscale >= 1");
+    // FFTUP_FLAG_ODD_SIZE: odd lengths are valid; `odd`: this plan has one (exact trigonometric resampling, kernels_odd.hpp).  A
+    // plan whose four lengths are even is the same plan with or without the flag.
+    const bool odd_len = (W & 1) || (H & 1) || (uW & 1) || (uH & 1);
+    const bool odd = odd_len && (cfg->flags & FFTUP_FLAG_ODD_SIZE);
+    if (W < 2 || H < 2 || uW < 2 || uH < 2 || (odd_len && !odd) || (!down && (uW < W || uH < H)))
+        return fail(FFTUP_E_INVALID_ARG, "width/height (and upscaled sizes) must be even, upscale >= 1; FFTUP_FLAG_ODD_SIZE accepts odd lengths");
     if (down && (uW < 2 || uH < 2 || uW >= W || uH >= H))
         return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the output sizes must be at least 2 and below the input's");
     // FFTUP_FLAG_ANY_SIZE: lengths with a prime factor above 7 run as Bluestein transforms; `bz`: this plan has one.  A plan
@@ -435,6 +439,15 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: a plan with a non-smooth length needs rows of at most 8192 points (no non-R2C or four-step path)");
         if (!bluestein_col_tk(H, uH))
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: a plan with a non-smooth length needs columns that fit the LDS (no four-step columns)");
+    }
+    if (odd) {
+        // the bounds of Bluestein plans (arithmetic on the sizes, before any device access): two-buffer R2C rows, columns in LDS
+        if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need even sizes (FFTUP_FLAG_ODD_SIZE covers the FFT modes only)");
+        if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_ODD_SIZE plans with an odd length exist for -p 0 and -p 2");
+        if (W > 8192u || uW > 8192u)
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ODD_SIZE: a plan with an odd length needs rows of at most 8192 points (no non-R2C or four-step path)");
+        if (!bluestein_col_tk(H, uH))
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ODD_SIZE: a plan with an odd length needs columns that fit the LDS (no four-step columns)");
     }
     // R2C rule of the reference: uW <= maxComputeSharedMemorySize/8 with 64 KB (VkResample.cpp:1424; complexSizeCalc = 16
     // for -p 1, VkResample.cpp:1334-1336, halves the limit); beyond it the full complex path runs
@@ -480,8 +493,11 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     P->dct = dct;
     P->down = down;
     P->bz = bz;
+    P->odd = odd;
     // (FFT downscale plans keep only the bins the output holds, kx <= uW/2: S1, S2 and the column pass shrink with the output)
+    // (odd plans: the bins both lengths hold, kx <= min(W, uW)/2 -- floor: an odd length has (n + 1)/2 bins from 0 up, no Nyquist bin)
     P->ncols = cplx ? (int)W : (down && !dct) ? (int)(uW / 2 + 1) : (int)(W / 2 + 1);
+    if (odd) P->ncols = (int)(std::min(W, uW) / 2 + 1);
     P->esz = P->dbl ? 8 : (P->half ? 2 : 4);
     P->csz = P->dbl ? 16 : 8;
     P->device = cfg->device;
@@ -535,7 +551,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             // u = 2 with the symmetric guard: the polyphase column kernel (k_col_poly: forward, phase, length-H inverse in ONE buffer of
             // H TK points, odd rows out; the C2R kernel takes the even rows from S1) where its stages run in place
             const char* const poly_e = fftup_jit::experiment("generic_poly");
-            if (!cplx && !dct && !down && is_smooth(H) && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
+            if (!cplx && !dct && !down && !odd && is_smooth(H) && uW == 2 * W && uH == 2 * H && P->zly == (int)(H / 2) && P->zry == (int)(uH - H / 2) && !(poly_e && atoi(poly_e) == 0)) {
                 for (int tk : {8, 4, 2, 1}) {
                     const size_t need = P->csz * (size_t)lpad_size((int)H * tk);
                     const int thr = inplace_threads(P->planH, tk, COL_INPLACE_PT, kernels_generic_max_threads(P->dbl));
@@ -553,8 +569,9 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                     if (ok) { P->TK = tk; P->ldsCol = need; P->inplaceC = true; P->thrCol = thr; break; }
                 }
             }
-            // a Bluestein column transform: buffers of L * TK points (bluestein_col_tk: checked before any device access)
-            if (!P->TK && (!is_smooth(H) || !is_smooth(uH))) {
+            // a Bluestein column transform: buffers of L * TK points (bluestein_col_tk: checked before any device access); the
+            // column kernel of an odd plan is sized the same way, max(length, L) * TK with L = length for a smooth one
+            if (!P->TK && (odd || !is_smooth(H) || !is_smooth(uH))) {
                 P->TK = bluestein_col_tk(H, uH);
                 P->ldsCol = 2 * P->csz * (size_t)lpad_size((int)(std::max(std::max(H, uH), std::max(lds_length(H, P->TK), lds_length(uH, P->TK))) * (uint32_t)P->TK));
                 if (P->ldsCol > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: this device's LDS does not hold the column transform"); goto bad; }
@@ -588,7 +605,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         if (P->mixed) { P->TK = 4; P->ldsCol = sizeof(float2) * (size_t)H * 4; }             // k_col_m: one in-place buffer
         // any other size with an integer or half-integer upscale factor: kernels specialised for it now (the counterpart
         // of VkFFT generating its shaders at plan time)
-        if (!P->dbl && !cplx && !dct && !down && !bz && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
+        if (!P->dbl && !cplx && !dct && !down && !bz && !odd && !P->tuned && !P->mixed && !(cfg->flags & (FFTUP_FLAG_GENERIC_KERNELS | FFTUP_FLAG_UNFUSED_SHARPEN)) && jit_enabled()) {
             int DD = 1;
             const int D = jit_factor(cfg->upscale, W, H, uW, uH, P->zly, P->zry, &DD);
             if (D) {
@@ -740,6 +757,9 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
     std::string s;
     if (P->down && P->dct) s = "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
                                + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
+    else if (P->odd) s = std::string(P->down ? "downscale: " : "") + "odd sizes: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
+                         + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH) + " (size-generic kernels, " + std::to_string(P->ncols)
+                         + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
     else if (P->down) s = "downscale: size-generic kernels, spectrum cropped to " + std::to_string(P->ncols) + " columns at the row stage (LDS ping-pong, "
                           "run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
     else if (P->dct) s = "dct: size-generic DCT-II / zero-pad / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
@@ -823,6 +843,11 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : P->down ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
     snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
+    // S1 / S2 above hold P->ncols columns: W/2 + 1 with W/2 rounded DOWN (an odd W has (W + 1)/2 bins, none self-paired); odd plans
+    // keep min(W, uW)/2 + 1.  The row kernels of an odd plan run (H + 1)/2 and (uH + 1)/2 workgroups per plane -- the rows are
+    // rounded UP to pairs, the bytes are not: the tail workgroup moves one row.  Their names (kernels_odd.hpp):
+    if (P->odd)
+        for (int i = 0; i < 3; i++) strncat(info->kernel_names[i], "_odd", 63 - strlen(info->kernel_names[i]));
     // kernels with a Bluestein transform (kernels_bluestein.hpp)
     const bool kbz[3] = {P->bzW.L != 0, P->bzH.L != 0 || P->bzUH.L != 0, P->bzUW.L != 0};
     for (int i = 0; i < 3; i++)

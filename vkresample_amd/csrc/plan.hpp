@@ -96,6 +96,9 @@ struct fftup_plan {
     // length L (kernels_bluestein.hpp); `bz`: the plan has at least one such transform (size-generic R2C kernels, fp32 arithmetic)
     BzPlan bzW{}, bzH{}, bzUW{}, bzUH{};
     bool bz = false;
+    // FFTUP_FLAG_ODD_SIZE with an odd W, H, uW or uH: exact trigonometric resampling on both axes (kernels_odd.hpp), up, down or
+    // -u 1; ncols = min(W, uW)/2 + 1 (floor); (rows + 1)/2 workgroups per plane in the row kernels
+    bool odd = false;
     int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
     int pairs_per_strip = 6;
     bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
