@@ -227,6 +227,35 @@ FFTUP_API int fftup_device_pci_bus_id(int device, char* buf, size_t buflen);
  * FFTUP_FLAG_ANY_SIZE lifts the smoothness rule for even lengths up to 4096 (Bluestein transforms, see the flag);
  * FFTUP_FLAG_ODD_SIZE accepts odd lengths (exact trigonometric resampling, see the flag). */
 FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
+/* EXTENSION: a plan for an exact output size, one factor per axis ("make this frame out_width x out_height": 1366x768 -> 1920x1080,
+ * anamorphic 720x576 -> 1920x1080, one axis only, one axis up and the other down).  cfg->upscale is ignored; every other field means
+ * what it means for fftup_plan_create, and the plan is an ordinary plan: every upload, execute, ring, submit, PNG, download,
+ * checksum, info and describe entry point works on it unchanged.
+ * Such a plan ALWAYS computes the exact trigonometric resampling written at FFTUP_FLAG_ODD_SIZE, on both axes, whatever the
+ * parities and whatever the direction of each axis (up on one, down or equal on the other); the quirks B1-B3 never apply.
+ * FFTUP_FLAG_ODD_SIZE and FFTUP_FLAG_DOWNSCALE are implied (accepted, they change nothing); FFTUP_FLAG_ANY_SIZE keeps its meaning
+ * (a length with a prime factor above 7 needs it and must be at most 4096: FFTUP_E_UNSUPPORTED_SIZE otherwise).
+ * align = FFTUP_ALIGN_CORNER: output pixel 0 on input pixel 0 (pixel m at input position m N / M), as every other FFT plan.
+ * align = FFTUP_ALIGN_CENTRE: pixel centres aligned, as OpenCV, PIL and FFTUP_FLAG_DCT place them: per axis N -> M, with
+ * d = (N/M - 1)/2, the bin of signed frequency f carries the extra factor exp(+2 pi i f d / N) (DFT with exp(-2 pi i nk / N)):
+ *   copied bins   Y[f mod M] = X[f mod N] exp(2 pi i f d / N);
+ *   split Nyquist bin (M > N, N even, h = N/2):    Y[h] = X[h] exp(+i phi) / 2,  Y[M-h] = X[h] exp(-i phi) / 2,  phi = 2 pi h d / N;
+ *   folded Nyquist bin (M < N, M even, h = M/2):   Y[h] = X[h] exp(+i phi) + X[N-h] exp(-i phi)  (real);
+ *   M = N: d = 0, nothing changes.
+ * Output pixel m then sits at input position (m + 1/2) N / M - 1/2: constants stay constant, a cosine of k cycles comes back as the
+ * same cosine sampled at those positions, and mirroring the input mirrors the output (under FFTUP_ALIGN_CORNER it does not).
+ * The pre-sharpen image is R = 1/(uW uH) IDFT(Y), the amplitude-preserving image y = R (uW uH) / (W H).  The sharpen pass is the
+ * existing one, unchanged (quirks B4, B5), with the effective factor u_e = (float)sqrt((double)uW uH / ((double)W H)) in the place
+ * of cfg->upscale: upsq = "%f"(u_e u_e), the product formed in fp32.
+ * Bounds (arithmetic on the sizes, decided before any device access; fftup_last_error names the rule): FFTUP_E_INVALID_ARG for a
+ * length below 2, align above 1, an output length outside [N/8, 8 N] on either axis, channels != 3, null pointers;
+ * FFTUP_E_UNSUPPORTED_PRECISION for -p 1; FFTUP_E_UNSUPPORTED_SIZE with FFTUP_FLAG_DCT, for rows above 8192 points and for columns
+ * whose transforms do not fit the compute unit's local memory (the odd-size plans' limits).  Four launches of the odd-size plans'
+ * kernels (fftup_info.tuned = u8_store = 0, names with "_odd", "_crop" on an axis that shrinks, "_bz" where a Bluestein transform
+ * runs).  fftup_version() is unchanged: detect the mode by this symbol. */
+enum { FFTUP_ALIGN_CORNER = 0, FFTUP_ALIGN_CENTRE = 1 };
+FFTUP_API int fftup_plan_create_size(fftup_plan** out, const fftup_config* cfg,
+                                     uint32_t out_width, uint32_t out_height, uint32_t align);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);
 FFTUP_API int fftup_plan_info(const fftup_plan* plan, fftup_info* info);

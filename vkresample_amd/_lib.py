@@ -21,6 +21,10 @@ FLAG_DOWNSCALE = 512              # upscale in [1/8, 1): spectrum cropped (older
 FLAG_ANY_SIZE = 1024              # even lengths with a prime factor above 7, up to 4096: Bluestein transforms (older libraries: FFTUP_E_UNSUPPORTED_SIZE)
 FLAG_ODD_SIZE = 2048              # odd widths and heights: exact trigonometric resampling per axis (older libraries: FFTUP_E_INVALID_ARG)
 
+# fftup_plan_create_size: where the output pixels sit
+ALIGN_CORNER = 0                  # output pixel 0 on input pixel 0, as every other FFT plan
+ALIGN_CENTRE = 1                  # pixel centres aligned: output pixel m at input position (m + 1/2) N / M - 1/2
+
 # every symbol include/fftup.h declares
 EXPORTS = [
     "fftup_device_count", "fftup_device_name", "fftup_plan_create", "fftup_plan_destroy", "fftup_plan_info",
@@ -29,6 +33,7 @@ EXPORTS = [
     "fftup_download_input_planar", "fftup_host_alloc", "fftup_host_free", "fftup_submit_rgb8", "fftup_wait",
     "fftup_drain", "fftup_strerror", "fftup_last_error", "fftup_version", "fftup_jit_check", "fftup_plan_describe",
     "fftup_device_pci_bus_id", "fftup_output_checksum", "fftup_png_bound", "fftup_submit_png", "fftup_wait_png",
+    "fftup_plan_create_size",
 ]
 ABI_VERSION = 2
 
@@ -68,6 +73,7 @@ def load():
     lib.fftup_device_count.restype = C.c_int
     lib.fftup_device_name.argtypes = [C.c_int, C.c_char_p, sz]
     lib.fftup_plan_create.argtypes = [C.POINTER(vp), C.POINTER(Config)]
+    lib.fftup_plan_create_size.argtypes = [C.POINTER(vp), C.POINTER(Config), u32, u32, u32]
     lib.fftup_plan_destroy.argtypes = [vp]
     lib.fftup_plan_destroy.restype = None
     lib.fftup_plan_info.argtypes = [vp, C.POINTER(Info)]

@@ -48,10 +48,25 @@ class Upscaler:
     and heights."""
 
     def __init__(self, width, height, upscale=2.0, precision=0, sharpen=0.2, device=0, flags=0, ring=1):
+        self._create(width, height, upscale, precision, sharpen, device, flags, ring, None)
+
+    @classmethod
+    def to_size(cls, width, height, out_width, out_height, precision=0, sharpen=0.2, device=0, flags=0, ring=1, align=0):
+        """A plan for an exact output size (fftup_plan_create_size): one factor per axis, each axis up, down or equal on its own,
+        exact trigonometric resampling on both.  `align`: ALIGN_CORNER (0, output pixel 0 on input pixel 0) or ALIGN_CENTRE (1, pixel
+        centres aligned, as OpenCV and PIL place them).  FLAG_ANY_SIZE is still needed for a length with a prime factor above 7."""
+        self = cls.__new__(cls)
+        self._create(width, height, 1.0, precision, sharpen, device, flags, ring, (out_width, out_height, align))
+        return self
+
+    def _create(self, width, height, upscale, precision, sharpen, device, flags, ring, size):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         cfg = _lib.Config(width, height, 3, upscale, precision, sharpen, device, flags, ring)
-        _check(self._lib.fftup_plan_create(C.byref(self._h), C.byref(cfg)), "fftup_plan_create")
+        if size is None:
+            _check(self._lib.fftup_plan_create(C.byref(self._h), C.byref(cfg)), "fftup_plan_create")
+        else:
+            _check(self._lib.fftup_plan_create_size(C.byref(self._h), C.byref(cfg), size[0], size[1], size[2]), "fftup_plan_create_size")
         info = _lib.Info()
         _check(self._lib.fftup_plan_info(self._h, C.byref(info)), "fftup_plan_info")
         if info.abi_version != _lib.ABI_VERSION:

@@ -19,6 +19,8 @@
 //   -anysize      FFTUP_FLAG_ANY_SIZE: even sizes with a prime factor above 7 (up to 4096 per such length) run as Bluestein transforms
 //   -oddsize      FFTUP_FLAG_ODD_SIZE: odd widths and heights, input or output (exact trigonometric resampling per axis)
 //   -downscale    FFTUP_FLAG_DOWNSCALE: -u in [1/8, 1) crops the spectrum (band-limited decimation; with -dct: truncated DCT)
+//   -size WxH     fftup_plan_create_size: the exact output size instead of -u, one factor per axis (each axis up, down or equal)
+//   -centres      with -size: pixel centres aligned (FFTUP_ALIGN_CENTRE) instead of pixel 0 on pixel 0
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -55,7 +57,16 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     std::atomic<int>* workQueue = nullptr;   // -workqueue: next file number - 1, shared by all threads
     bool stageTimes = false;                 // -stagetimes: per-thread host time by stage (batched mode)
     bool gpuPng = false;                     // -gpupng: batched mode: the GPU delivers the finished PNG (fftup_submit_png)
+    uint32_t outWidth = 0, outHeight = 0;    // -size WxH (0: none, the output size follows from -u)
+    uint32_t align = FFTUP_ALIGN_CORNER;     // -centres
 };
+
+// fftup_plan_create, or fftup_plan_create_size under -size
+static int create_plan(const ResampleConfiguration& config, fftup_plan** plan, const fftup_config& cfg)
+{
+    if (config.outWidth) return fftup_plan_create_size(plan, &cfg, config.outWidth, config.outHeight, config.align);
+    return fftup_plan_create(plan, &cfg);
+}
 
 static bool findFlag(char** start, char** end, const std::string& flag)      // VR:1782-1784: exact token match
 {
@@ -94,12 +105,12 @@ static double now_ms()
 struct SharedPlan { fftup_plan* plan = nullptr; fftup_info info{}; };
 static std::mutex g_plans_mu;
 static std::map<std::tuple<int, int, int>, SharedPlan> g_plans;
-static int shared_plan(const fftup_config& cfg, SharedPlan* out)
+static int shared_plan(const ResampleConfiguration& config, const fftup_config& cfg, SharedPlan* out)
 {
     std::lock_guard<std::mutex> lock(g_plans_mu);
     SharedPlan& sp = g_plans[std::make_tuple((int)cfg.device, (int)cfg.width, (int)cfg.height)];
     if (!sp.plan) {
-        const int res = fftup_plan_create(&sp.plan, &cfg);
+        const int res = create_plan(config, &sp.plan, cfg);
         if (res != FFTUP_OK) { sp.plan = nullptr; return res; }
         fftup_plan_info(sp.plan, &sp.info);
     }
@@ -181,10 +192,10 @@ static int launchResample(ResampleConfiguration config)                      // 
     int res;
     if (streamed) {
         SharedPlan sp;
-        res = shared_plan(cfg, &sp);
+        res = shared_plan(config, cfg, &sp);
         plan = sp.plan; info = sp.info;
     } else {
-        res = fftup_plan_create(&plan, &cfg);
+        res = create_plan(config, &plan, cfg);
         if (res == FFTUP_OK) fftup_plan_info(plan, &info);
     }
     if (res != FFTUP_OK) {
@@ -291,7 +302,9 @@ static int launchResample(ResampleConfiguration config)                      // 
             fftup_plan_destroy(plan);
             return res;
         }
-        if (!config.fileUpload)
+        if (!config.fileUpload && config.outWidth)
+            printf("VkResample exact size%s: %dx%d to %dx%d Time: %0.3f ms\n", config.align == FFTUP_ALIGN_CENTRE ? " (centres)" : "", width, height, uW, uH, totTime);
+        else if (!config.fileUpload)
             printf("VkResample %0.1fx upscale: %dx%d to %dx%d Time: %0.3f ms\n", config.upscale, width, height, uW, uH, totTime);   // VR:1694
         res = fftup_download_rgb8(plan, 0, png_output.data(), (size_t)uW * 3);  // transferDataToCPU + unpack loop
         if (res != FFTUP_OK) {
@@ -350,6 +363,8 @@ int main(int argc, char* argv[])
         printf("	-anysize: accept even sizes that do not factor into 2,3,5,7 (each such length up to 4096; Bluestein transforms; -p 0 and -p 2, not with -dct)\n");
         printf("	-oddsize: accept odd widths and heights, e.g. 853x480 or -u 1.5 on 62x38: exact trigonometric resampling (-p 0 and -p 2, not with -dct; with -anysize: any length up to 4096)\n");
         printf("	-downscale: allow -u in [1/8, 1), e.g. -u 1/2: spectral downscale (band-limited, no aliasing; -p 0 and -p 2; with -dct: DCT downscale)\n");
+        printf("	-size WxH: the exact output size instead of -u, e.g. -size 1920x1080 on 1366x768: one factor per axis, each between 1/8 and 8, up or down (exact trigonometric resampling; -p 0 and -p 2, not with -dct or -u; -anysize for lengths with prime factors above 7)\n");
+        printf("	-centres: with -size: align the pixel centres, as other resizers do (default: output pixel 0 on input pixel 0)\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -374,7 +389,19 @@ int main(int argc, char* argv[])
         if (v) sscanf(v, "%f", &config.sharpenConst);
         else { printf("No sharpening parameter is selected with -s flag\n"); return 1; }
     }
-    if (findFlag(B, E, "-u")) {
+    if (findFlag(B, E, "-size")) {
+        char* v = getFlagValue(B, E, "-size");
+        char tail = 0;
+        if (findFlag(B, E, "-u")) { printf("-size gives the output size: it cannot be combined with -u\n"); return 1; }
+        if (!v || sscanf(v, "%ux%u%c", &config.outWidth, &config.outHeight, &tail) != 2 || !config.outWidth || !config.outHeight) {
+            printf("No proper output size is selected with -size flag (WxH, e.g. 1920x1080)\n");
+            return 1;
+        }
+        if (findFlag(B, E, "-centres")) config.align = FFTUP_ALIGN_CENTRE;
+    } else if (findFlag(B, E, "-centres")) {
+        printf("-centres needs an output size given with -size\n");
+        return 1;
+    } else if (findFlag(B, E, "-u")) {
         char* v = getFlagValue(B, E, "-u");
         // (VR:1883: "%f".  Extension: "-u 4/3" -- a ratio, divided in float: the nearest float of 4/3 is what makes 1920 x 1080 come out
         // as exactly 2560 x 1440 in the reference's float arithmetic; typed as a decimal it takes eight digits, 1.3333334)

@@ -543,6 +543,7 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
 
 // FFTUP_FLAG_ODD_SIZE with an odd length: row R2C keeping kx <= min(W, uW)/2 -> column forward / bin map / inverse -> row C2R ->
 // sharpen (kernels_odd.hpp).  Up, down or -u 1; (rows + 1) / 2 workgroups per plane, the last one with a single row when odd.
+// Plans of fftup_plan_create_size run the same four launches, each axis with its own direction, centre-aligned ones with phase tables.
 static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
     hipStream_t st = P->lanes[P->cur].stream;
@@ -551,7 +552,7 @@ static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
     if (which < 0 || which == 0) {
         OddRowParams p{};
         p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
-        p.TK = P->TK; p.NT = P->NT; p.kmax = kmax; p.fold = (P->uW < P->W && !(P->uW & 1)) ? 1 : 0; p.bz = P->bzW;
+        p.TK = P->TK; p.NT = P->NT; p.kmax = kmax; p.fold = (P->uW < P->W && !(P->uW & 1)) ? 1 : 0; p.bz = P->bzW; p.ph = P->phW;
         const dim3 grid((P->H + 1) / 2, 3), block(P->thrW);
         if (kind == 2) {
             p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
@@ -567,7 +568,7 @@ static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
         OddColParams p{};
         p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
         p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
-        p.bzH = P->bzH; p.bzUH = P->bzUH;
+        p.bzH = P->bzH; p.bzUH = P->bzUH; p.ph = P->phH;
         const dim3 grid(P->NT, 3), block(P->thrCol);
         switch (P->TK) {
         case 8: hipLaunchKernelGGL(k_col_odd<8>, grid, block, P->ldsCol, st, p); break;

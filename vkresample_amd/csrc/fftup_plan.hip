@@ -397,10 +397,44 @@ static int inplace_threads(const StagePlan& sp, int tk, int pt, int tmax)
     return thr <= tmax ? (int)thr : 0;
 }
 
-int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
+// Centre alignment of one axis N -> M (kernels_odd.hpp): ph[k] = exp(-2 pi i k d / N), d = (N/M - 1)/2, k = 0 .. min(N, M)/2, in
+// double, rounded once to fp32 (as make_twiddles).  The phase is -pi k (N - M) / (M N): k (N - M) is reduced modulo 2 M N in
+// 64-bit integers BEFORE the division, as the chirp tables' (it reaches hundreds of radians).  M == N: no table (d = 0).
+static int make_phases(fftup_plan* P, float2** dptr, uint32_t N, uint32_t M)
 {
-    if (!out || !cfg) return fail(FFTUP_E_INVALID_ARG, "null argument");
+    *dptr = nullptr;
+    if (N == M) return FFTUP_OK;
+    const uint32_t n = std::min(N, M) / 2 + 1;
+    const int64_t period = 2 * (int64_t)M * (int64_t)N;
+    std::vector<float2> h(n);
+    for (uint32_t k = 0; k < n; k++) {
+        int64_t r = ((int64_t)k * ((int64_t)N - (int64_t)M)) % period;         // in (-period, period)
+        if (r > period / 2) r -= period;
+        if (r < -period / 2) r += period;
+        const double a = -M_PI * (double)r / ((double)M * (double)N);
+        h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
+    }
+    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
+    return FFTUP_OK;
+}
+
+// fftup_plan_create (size == nullptr: the output size follows from cfg->upscale) and fftup_plan_create_size (size = {uW, uH},
+// cfg->upscale ignored)
+static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint32_t* size, uint32_t align)
+{
+    if (!out || !cfg_in) return fail(FFTUP_E_INVALID_ARG, "null argument");
     *out = nullptr;
+    const bool exact = size != nullptr;
+    fftup_config cfg_copy = *cfg_in;
+    if (exact) {
+        // the effective factor u_e = sqrt(uW uH / (W H)) takes the place of cfg->upscale in the sharpen constant (and only there);
+        // 1 until the sizes below are known to be valid
+        cfg_copy.upscale = 1.0f;
+        cfg_copy.flags &= ~(uint32_t)FFTUP_FLAG_DOWNSCALE;       // (implied per axis: accepted, changes nothing)
+    }
+    const fftup_config* const cfg = &cfg_copy;
     if (cfg->channels != 3) return fail(FFTUP_E_INVALID_ARG, "channels must be 3 (VkResample.cpp:1368)");
     if (cfg->precision > 2) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "precision must be 0 (single), 1 (double) or 2 (half)");
     const uint32_t W = cfg->width, H = cfg->height;
@@ -412,13 +446,22 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     if (W > (1u << 16) || H > (1u << 16)) return fail(FFTUP_E_INVALID_ARG, "width/height above 65536");
     if (cfg->ring > 1024) return fail(FFTUP_E_INVALID_ARG, "ring must be <= 1024");
     if (!(cfg->sharpen == cfg->sharpen)) return fail(FFTUP_E_INVALID_ARG, "sharpen is NaN");
-    const uint32_t uW = (uint32_t)(cfg->upscale * (float)W);     // VkResample.cpp:1417-1418
-    const uint32_t uH = (uint32_t)(cfg->upscale * (float)H);
+    const uint32_t uW = exact ? size[0] : (uint32_t)(cfg->upscale * (float)W);     // VkResample.cpp:1417-1418
+    const uint32_t uH = exact ? size[1] : (uint32_t)(cfg->upscale * (float)H);
+    if (exact) {
+        // fftup_plan_create_size: each axis on its own, up, down or equal, either parity (arithmetic on the sizes)
+        if (W < 2 || H < 2 || uW < 2 || uH < 2) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: every length (width, height, out_width, out_height) must be at least 2");
+        if (align > FFTUP_ALIGN_CENTRE) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: align must be FFTUP_ALIGN_CORNER (0) or FFTUP_ALIGN_CENTRE (1)");
+        if (8 * (uint64_t)uW < W || uW > 8 * (uint64_t)W) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: out_width must lie in [width/8, 8 width]");
+        if (8 * (uint64_t)uH < H || uH > 8 * (uint64_t)H) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: out_height must lie in [height/8, 8 height]");
+        cfg_copy.upscale = (float)std::sqrt((double)uW * (double)uH / ((double)W * (double)H));
+    }
     // FFTUP_FLAG_ODD_SIZE: odd lengths are valid; `odd`: this plan has one (exact trigonometric resampling, kernels_odd.hpp).  A
     // plan whose four lengths are even is the same plan with or without the flag.
     const bool odd_len = (W & 1) || (H & 1) || (uW & 1) || (uH & 1);
-    const bool odd = odd_len && (cfg->flags & FFTUP_FLAG_ODD_SIZE);
-    if (W < 2 || H < 2 || uW < 2 || uH < 2 || (odd_len && !odd) || (!down && (uW < W || uH < H)))
+    // (fftup_plan_create_size: always that rule, whatever the parities, FFTUP_FLAG_ODD_SIZE implied)
+    const bool odd = exact || (odd_len && (cfg->flags & FFTUP_FLAG_ODD_SIZE));
+    if (!exact && (W < 2 || H < 2 || uW < 2 || uH < 2 || (odd_len && !odd) || (!down && (uW < W || uH < H))))
         return fail(FFTUP_E_INVALID_ARG, "width/height (and upscaled sizes) must be even, upscale >= 1; FFTUP_FLAG_ODD_SIZE accepts odd lengths");
     if (down && (uW < 2 || uH < 2 || uW >= W || uH >= H))
         return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the output sizes must be at least 2 and below the input's");
@@ -440,7 +483,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         if (!bluestein_col_tk(H, uH))
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: a plan with a non-smooth length needs columns that fit the LDS (no four-step columns)");
     }
-    if (odd) {
+    if (odd && !exact) {
         // the bounds of Bluestein plans (arithmetic on the sizes, before any device access): two-buffer R2C rows, columns in LDS
         if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need even sizes (FFTUP_FLAG_ODD_SIZE covers the FFT modes only)");
         if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_ODD_SIZE plans with an odd length exist for -p 0 and -p 2");
@@ -448,6 +491,15 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ODD_SIZE: a plan with an odd length needs rows of at most 8192 points (no non-R2C or four-step path)");
         if (!bluestein_col_tk(H, uH))
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ODD_SIZE: a plan with an odd length needs columns that fit the LDS (no four-step columns)");
+    }
+    if (exact) {
+        // the same bounds: these plans run the odd-size plans' kernels
+        if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_size covers the FFT mode only (no FFTUP_FLAG_DCT)");
+        if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "fftup_plan_create_size plans exist for -p 0 and -p 2");
+        if (W > 8192u || uW > 8192u)
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_size: rows of at most 8192 points (no non-R2C or four-step path)");
+        if (!bluestein_col_tk(H, uH))
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_size: the columns must fit the LDS (no four-step columns)");
     }
     // R2C rule of the reference: uW <= maxComputeSharedMemorySize/8 with 64 KB (VkResample.cpp:1424; complexSizeCalc = 16
     // for -p 1, VkResample.cpp:1334-1336, halves the limit); beyond it the full complex path runs
@@ -494,6 +546,8 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
     P->down = down;
     P->bz = bz;
     P->odd = odd;
+    P->exact = exact;
+    P->align = exact ? align : 0;
     // (FFT downscale plans keep only the bins the output holds, kx <= uW/2: S1, S2 and the column pass shrink with the output)
     // (odd plans: the bins both lengths hold, kx <= min(W, uW)/2 -- floor: an odd length has (n + 1)/2 bins from 0 up, no Nyquist bin)
     P->ncols = cplx ? (int)W : (down && !dct) ? (int)(uW / 2 + 1) : (int)(W / 2 + 1);
@@ -528,8 +582,8 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         P->zlx = (int)(W / 2);
         P->zrx = cplx ? (int)(uint32_t)((2 * u - 1) * (float)uW / (2 * u)) : (int)(uW / 2);      // VR:1498 / VR:1493
         // (downscale plans have no padding: no guard, and 2u - 1 < 0 would make the cast below undefined)
-        P->zly = down ? 0 : (int)(uint32_t)((float)uH / (2 * u));
-        P->zry = down ? 0 : (int)(uint32_t)((2 * u - 1) * (float)uH / (2 * u));
+        P->zly = (down || exact) ? 0 : (int)(uint32_t)((float)uH / (2 * u));
+        P->zry = (down || exact) ? 0 : (int)(uint32_t)((2 * u - 1) * (float)uH / (2 * u));
 
         P->planW = make_stage_plan(W);
         P->planH = make_stage_plan(H);
@@ -541,7 +595,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
         // (experiment aot=0: the sizes with ahead-of-time kernels go through the plan-time compiler as well)
         const char* const aot_e = fftup_jit::experiment("aot");
         const bool aot = !(aot_e && atoi(aot_e) == 0);
-        P->tuned = aot && !P->dbl && !cplx && !dct && !down && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
+        P->tuned = aot && !P->dbl && !cplx && !dct && !down && !exact && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H &&
                    (W == 512 || W == 1024 || W == 2048) && (H == 256 || H == 512 || H == 1024);
         P->TK = 0;
         if (P->tuned) {
@@ -599,7 +653,7 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                 f.thrB = std::min(tmax, std::max(64, round_up(f.n2 * f.tkb / 8, 64)));
             }
         }
-        if (aot && !P->dbl && !cplx && !dct && !down && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
+        if (aot && !P->dbl && !cplx && !dct && !down && !exact && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
             P->mixed = kernels_aot_mixed_plan(W, H);                    // 1920x1080, 1280x720
         }
         if (P->mixed) { P->TK = 4; P->ldsCol = sizeof(float2) * (size_t)H * 4; }             // k_col_m: one in-place buffer
@@ -687,6 +741,10 @@ int fftup_plan_create(fftup_plan** out, const fftup_config* cfg)
                     PLAN_RC(make_bluestein(P, axes[i].first, axes[i].second, L, make_stage_plan(L)));
                 }
         }
+        if (exact && align == FFTUP_ALIGN_CENTRE) {
+            PLAN_RC(make_phases(P, &P->phW, W, uW));
+            PLAN_RC(make_phases(P, &P->phH, H, uH));
+        }
         if (dct) {
             PLAN_RC(make_rotations(P, &P->rotW, W));
             PLAN_RC(make_rotations(P, &P->rotH, H));
@@ -751,12 +809,24 @@ bad:
 #undef PLAN_RC
 }
 
+int fftup_plan_create(fftup_plan** out, const fftup_config* cfg) { return plan_create(out, cfg, nullptr, 0); }
+
+int fftup_plan_create_size(fftup_plan** out, const fftup_config* cfg, uint32_t out_width, uint32_t out_height, uint32_t align)
+{
+    const uint32_t size[2] = {out_width, out_height};
+    return plan_create(out, cfg, size, align);
+}
+
 int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
 {
     if (!P || !buf || !buflen) return fail(FFTUP_E_INVALID_ARG, "null argument");
     std::string s;
     if (P->down && P->dct) s = "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
                                + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
+    else if (P->exact) s = "exact size: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
+                           + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH)
+                           + (P->align == FFTUP_ALIGN_CENTRE ? ", pixel centres aligned" : ", pixel 0 on pixel 0") + " (size-generic kernels, " + std::to_string(P->ncols)
+                           + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
     else if (P->odd) s = std::string(P->down ? "downscale: " : "") + "odd sizes: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
                          + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH) + " (size-generic kernels, " + std::to_string(P->ncols)
                          + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
@@ -839,8 +909,10 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     info->abi_version = FFTUP_ABI_VERSION;
     info->u8_store = P->u8out ? 1 : 0;
     snprintf(info->device_name, sizeof info->device_name, "%s", device_label(P->prop));
-    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : P->down ? "row_r2c_crop" : P->cplx ? "row_c2c" : "row_r2c");
-    snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : P->down ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
+    // (fftup_plan_create_size: the direction is a property of the axis, the row kernel crops when uW < W, the column kernel when uH < H)
+    const bool crop_rows = P->exact ? P->uW < P->W : P->down, crop_cols = P->exact ? P->uH < P->H : P->down;
+    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : crop_rows ? "row_r2c_crop" : P->cplx ? "row_c2c" : "row_r2c");
+    snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : crop_cols ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
     snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
     // S1 / S2 above hold P->ncols columns: W/2 + 1 with W/2 rounded DOWN (an odd W has (W + 1)/2 bins, none self-paired); odd plans

@@ -16,6 +16,13 @@
 //   * the half spectrum holds kx = 0 .. min(W, uW)/2 (floor): W/2 + 1 columns of an odd W, none of them self-paired.
 //   * the bin map above instead of the reference's shift and read guard; the zero rows and columns are never stored.
 //   * scalar stores of the binary16 image: with an odd uW every second row of a plane starts on a 2-byte boundary only.
+// CENTRE ALIGNMENT (fftup_plan_create_size, FFTUP_ALIGN_CENTRE): per axis N -> M the output pixel m sits at input position
+// (m + 1/2) N / M - 1/2 instead of m N / M -- a shift by d = (N/M - 1)/2 input pixels, i.e. the factor exp(+2 pi i f d / N) on the bin
+// of signed frequency f of the DFT with exp(-2 pi i nk / N).  The forward transforms here run with exp(+2 pi i nk / N) (fft_any<+1>),
+// so bin k of these kernels holds the frequency -k: the table `ph` of an axis holds ph[k] = exp(-2 pi i k d / N), k = 0 .. min(N, M)/2,
+// the factor of kernel bin +k; bin -k takes its conjugate.  The split Nyquist bin keeps its two different halves, X[h] ph[h] / 2 and
+// X[h] conj(ph[h]) / 2, the folded one becomes X[h] ph[h] + X[N-h] conj(ph[h]).  ph == nullptr (corner alignment, or M == N):
+// nothing is multiplied, the kernels compute what they computed before the table existed.
 // New parameter structs live here: kernels_generic.hpp and its neighbours are embedded for the plan-time compiler and
 // fingerprinted by the committed counter profiles, and stay byte-identical.  fp32 arithmetic only (-p 0 and -p 2).
 #pragma once
@@ -40,7 +47,10 @@ struct OddRowParams {
     int kmax;                // the last bin kept: min(W, uW) / 2
     int fold;                // 1: uW < W and uW even -- bin kmax is the output's Nyquist bin, stored folded: X[h] + X[W-h] = 2 Re X[h]
     BzPlan bz;               // L != 0: the rows run as Bluestein transforms
+    const float2* ph;        // centre alignment: kmax + 1 phase factors (see above), or nullptr
 };
+
+__device__ __forceinline__ float2 cconj(float2 a) { return make_float2(a.x, -a.y); }
 
 // grid ((H + 1) / 2, 3); dynamic LDS = 2 * lpad_size(max(W, bz.L)) complex.  Rows 2j (real part) and 2j+1 (imaginary part; the
 // tail row of an odd H has none: zero)
@@ -67,6 +77,8 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_r2c_od
         const float2 zn = Z[lpad(k == 0 ? 0 : W - k)];
         float2 A = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
         float2 B = make_float2(0.5f * (zk.y + zn.y), 0.5f * (-zk.x + zn.x));
+        // (both rows are real: their bins take the same factor, and the folded bin X[h] w + conj(X[h] w) stays 2 Re)
+        if (p.ph) { const float2 w = p.ph[k]; A = cmul(A, w); B = cmul(B, w); }
         if (p.fold && k == p.kmax) { A = make_float2(2.f * A.x, 0.f); B = make_float2(2.f * B.x, 0.f); }
         float2* dst = base + (long)(k / p.TK) * tile_stride + (long)(2 * j) * p.TK + (k % p.TK);
         dst[0] = A;
@@ -84,6 +96,7 @@ struct OddColParams {
     int ncols;               // kx columns present: min(W, uW)/2 + 1
     float inv_norm;          // 1/uH
     BzPlan bzH, bzUH;        // per transform, L = 0 for a smooth length
+    const float2* ph;        // centre alignment: min(H, uH)/2 + 1 phase factors (see above), or nullptr
 };
 
 // grid (NT, 3); dynamic LDS = 2 * lpad_size(max(H, uH, bzH.L, bzUH.L) * TK) complex.  Forward length H, the bin map, inverse length
@@ -112,11 +125,21 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_odd(Od
         const int ky = e / TK, col = e % TK;
         const int f = 2 * ky < uH ? ky : ky - uH, af = f < 0 ? -f : f;
         float2 v = make_float2(0.f, 0.f);
-        if (2 * af < K) v = F[lpad((f < 0 ? H + f : f) * TK + col)];
+        if (2 * af < K) {
+            v = F[lpad((f < 0 ? H + f : f) * TK + col)];
+            if (p.ph) v = cmul(v, f < 0 ? cconj(p.ph[af]) : p.ph[af]);
+        }
         else if (2 * af == K) {                                          // the Nyquist bin of the shorter, even length
-            const float2 lo = F[lpad(af * TK + col)];
-            if (uH > H) v = cscale(lo, 0.5f);                            // split: ky = H/2 and ky = uH - H/2
-            else if (uH < H) v = cadd(lo, F[lpad((H - af) * TK + col)]); // folded (ky = uH/2 only)
+            float2 lo = F[lpad(af * TK + col)];
+            if (uH > H) {                                                // split: ky = H/2 and ky = uH - H/2
+                if (p.ph) lo = cmul(lo, f < 0 ? cconj(p.ph[af]) : p.ph[af]);
+                v = cscale(lo, 0.5f);
+            }
+            else if (uH < H) {                                           // folded (ky = uH/2 only)
+                float2 hi = F[lpad((H - af) * TK + col)];
+                if (p.ph) { lo = cmul(lo, p.ph[af]); hi = cmul(hi, cconj(p.ph[af])); }
+                v = cadd(lo, hi);
+            }
             else v = lo;
         }
         G[lpad(e)] = v;
@@ -136,7 +159,8 @@ struct OddC2RParams {
     int uW, uH;
     int TK, NT;
     int kmax;                // the last bin the spectrum holds: min(W, uW) / 2
-    int halve;               // 1: uW > W and W even -- bin kmax is the input's Nyquist bin, split: Y[h] = Y[uW-h] = X[h] / 2
+    int halve;               // 1: uW > W and W even -- bin kmax is the input's Nyquist bin, split: Y[h] = Y[uW-h] = X[h] / 2 (with centre
+                             // alignment it carries its phase, X[h] ph[h]: the loop below writes bin uW - h as its conjugate, as for any k)
     float inv_norm;          // 1/uW
     BzPlan bz;               // L != 0: the rows run as Bluestein transforms
 };

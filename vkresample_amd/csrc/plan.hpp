@@ -99,6 +99,11 @@ struct fftup_plan {
     // FFTUP_FLAG_ODD_SIZE with an odd W, H, uW or uH: exact trigonometric resampling on both axes (kernels_odd.hpp), up, down or
     // -u 1; ncols = min(W, uW)/2 + 1 (floor); (rows + 1)/2 workgroups per plane in the row kernels
     bool odd = false;
+    // fftup_plan_create_size: the output size is given per axis (always `odd`'s kernels, each axis up, down or equal on its own);
+    // align = FFTUP_ALIGN_CENTRE: phase tables of the axes whose lengths differ (kernels_odd.hpp), nullptr otherwise
+    bool exact = false;
+    uint32_t align = 0;
+    float2 *phW = nullptr, *phH = nullptr;
     int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
     int pairs_per_strip = 6;
     bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
