@@ -369,6 +369,71 @@ FFTUP_API int fftup_submit_png(fftup_plan* plan, const uint8_t* rgb_in, size_t i
                                uint64_t* ticket);
 FFTUP_API int fftup_wait_png(fftup_plan* plan, uint64_t ticket, uint8_t* png_out, size_t capacity, size_t* png_bytes);
 
+/* EXTENSION: frames that never leave the GPU.  fftup_execute_device runs the plan on CALLER-OWNED device memory: frame i reads the
+ * W x H image in[i] and writes the uW x uH image out[i].  No ring slot is read or written (fftup_download_planar / _rgb8 /
+ * fftup_output_checksum of a slot keep returning what the last fftup_execute / _ring / submit left there); after the call
+ * fftup_download_presharpen returns the tap of the call's last frame.  Every plan kind and precision is accepted.
+ * Detect the feature by this symbol; fftup_version(), FFTUP_ABI_VERSION, fftup_config and fftup_info are unchanged.
+ *
+ * Formats.  FFTUP_FMT_RGB8: interleaved 8-bit RGB, as fftup_upload_rgb8 / fftup_download_rgb8 take and give it (input: the
+ * conversion of VR:1636-1688, in the row kernel with FFTUP_FLAG_FUSE_U8_LOAD; output: u8 = trunc(255 x), saturating unless
+ * FFTUP_FLAG_U8_WRAP).  FFTUP_FMT_PLANAR: 3 planes in the plan's storage type, as fftup_upload_planar / fftup_download_planar.
+ * The results are, byte for byte, those of upload -> fftup_execute(1) -> download on the same plan.
+ *
+ * Ordering.  The call is asynchronous to the host and never synchronises it.  All of its work starts after everything enqueued
+ * on `stream` before the call, and everything enqueued on `stream` after the call returns starts after the call's last kernel (one
+ * event recorded on `stream` that every lane used waits for; one completion event per lane used that `stream` waits for).  The
+ * caller keeps the memory of `in` and `out` alive and untouched until `stream` has passed that point; the descriptor arrays
+ * themselves are read before the call returns.  Consecutive frames alternate on the plan's FFTUP_STREAMS lanes exactly as in
+ * fftup_execute_ring, so a batch overlaps like that call's.  One host thread per plan at a time, as for fftup_execute; entry
+ * points of the same plan called later are ordered behind the call.
+ *
+ * In place, or through one staging kernel (the output bytes are the same either way):
+ *   PLANAR input  -- read in place by the frame's first kernel, with the caller's strides, on every plan kind: all first kernels
+ *                    load single elements at 64-bit offsets, so `data` only has to be a multiple of the element size (strides
+ *                    are, by the rules below).  Otherwise one strided gather into a per-lane staging buffer.
+ *   RGB8 input    -- read in place by the row kernel on plans with FFTUP_FLAG_FUSE_U8_LOAD (-p 0 / -p 2), any address and
+ *                    stride; otherwise one conversion kernel from the caller's rows into the per-lane staging planes.
+ *   PLANAR output -- written in place by the frame's last kernel when the image is dense (row_stride_bytes = uW * element size,
+ *                    plane_stride_bytes = uW * uH * element size) and `data` is 16-byte aligned (the last kernels store up to 16
+ *                    bytes at once).  Otherwise the frame goes to a per-lane scratch image and one strided scatter.
+ *   RGB8 output   -- fftup_info.u8_store == 1: written in place by the fused kernel when the rows are dense (3 * uW bytes),
+ *                    through the lane scratch and a strided byte copy otherwise.  Other plans: the conversion kernel writes the
+ *                    caller's rows, any stride, from the lane scratch image.
+ * Staging and scratch buffers are allocated by the first call that needs them and freed with the plan.
+ * Containment: the library never writes a byte of caller memory outside the `height` rows of `width` pixels a descriptor names --
+ * no row padding, no plane padding, nothing in front of `data` or behind the last row.
+ *
+ * Validation happens before any launch; on failure nothing is enqueued.  FFTUP_E_INVALID_ARG (fftup_last_error names the rule
+ * and the image): a null pointer; n_frames == 0; an unknown format; a row stride below one row or, PLANAR, a stride that is not a
+ * multiple of the element size or a plane stride below height * row_stride_bytes; PLANAR output on a plan with
+ * fftup_info.u8_store == 1 (it has no planes: the rule of fftup_download_planar); `data` that hipPointerGetAttributes does not
+ * report as device memory of the plan's device (host pointers, other devices).  No check reads or writes the memory itself.
+ * The memory must come from the HIP runtime this library is linked to: a process that holds a second copy of the runtime (a
+ * Python wheel that bundles its own libamdhip64, say) cannot hand that copy's pointers or streams to this call. */
+enum { FFTUP_FMT_RGB8 = 0,     /* interleaved 8-bit RGB, rows of row_stride_bytes >= 3*width; plane_stride_bytes ignored */
+       FFTUP_FMT_PLANAR = 1 }; /* 3 planes in the plan's storage type (float -p 0, double -p 1, IEEE half -p 2) */
+typedef struct fftup_device_image {
+    void*    data;               /* device memory of the plan's device */
+    uint32_t format;             /* FFTUP_FMT_* */
+    size_t   row_stride_bytes;   /* >= one row; PLANAR: a multiple of the element size */
+    size_t   plane_stride_bytes; /* PLANAR: >= height*row_stride_bytes, a multiple of the element size */
+} fftup_device_image;
+
+/* n_frames frames: frame i reads in[i] (W x H) and writes out[i] (uW x uH).  Asynchronous to the host. */
+FFTUP_API int fftup_execute_device(fftup_plan* plan, const fftup_device_image* in, const fftup_device_image* out,
+                                   uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
+
+/* The device-side siblings of fftup_host_alloc, for hosts without HIP bindings (ctypes, tests): device memory and streams of the
+ * runtime this library uses.  fftup_device_alloc: NULL on failure (fftup_last_error).  fftup_device_copy: kind 0 host to device,
+ * 1 device to host, 2 device to device; enqueued on `stream` (NULL = the default stream), then waits for `stream`: blocking.
+ * fftup_stream_create: a non-blocking stream of `device` (FFTUP_E_NO_DEVICE: bad device id); fftup_stream_destroy waits for it first. */
+FFTUP_API void* fftup_device_alloc(int device, size_t bytes);
+FFTUP_API void fftup_device_free(void* ptr);
+FFTUP_API int fftup_device_copy(void* dst, const void* src, size_t bytes, int kind, void* stream);
+FFTUP_API int fftup_stream_create(int device, void** stream);
+FFTUP_API int fftup_stream_destroy(void* stream);
+
 FFTUP_API const char* fftup_strerror(int code);
 FFTUP_API const char* fftup_last_error(void);   /* thread-local detail of the last failure */
 FFTUP_API const char* fftup_version(void);

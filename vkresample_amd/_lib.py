@@ -25,6 +25,10 @@ FLAG_ODD_SIZE = 2048              # odd widths and heights: exact trigonometric 
 ALIGN_CORNER = 0                  # output pixel 0 on input pixel 0, as every other FFT plan
 ALIGN_CENTRE = 1                  # pixel centres aligned: output pixel m at input position (m + 1/2) N / M - 1/2
 
+# fftup_device_image.format (fftup_execute_device)
+FMT_RGB8 = 0                      # interleaved 8-bit RGB, rows of row_stride_bytes
+FMT_PLANAR = 1                    # 3 planes in the plan's storage type
+
 # every symbol include/fftup.h declares
 EXPORTS = [
     "fftup_device_count", "fftup_device_name", "fftup_plan_create", "fftup_plan_destroy", "fftup_plan_info",
@@ -33,7 +37,8 @@ EXPORTS = [
     "fftup_download_input_planar", "fftup_host_alloc", "fftup_host_free", "fftup_submit_rgb8", "fftup_wait",
     "fftup_drain", "fftup_strerror", "fftup_last_error", "fftup_version", "fftup_jit_check", "fftup_plan_describe",
     "fftup_device_pci_bus_id", "fftup_output_checksum", "fftup_png_bound", "fftup_submit_png", "fftup_wait_png",
-    "fftup_plan_create_size",
+    "fftup_plan_create_size", "fftup_execute_device", "fftup_device_alloc", "fftup_device_free", "fftup_device_copy",
+    "fftup_stream_create", "fftup_stream_destroy",
 ]
 ABI_VERSION = 2
 
@@ -51,6 +56,11 @@ class Info(C.Structure):
                 ("device_name", C.c_char * 256), ("kernel_names", (C.c_char * 64) * FFTUP_NUM_KERNELS),
                 # appended in ABI version 2
                 ("kernel_min_bytes", C.c_double * FFTUP_NUM_KERNELS), ("abi_version", C.c_uint32), ("u8_store", C.c_uint32)]
+
+
+class DeviceImageDesc(C.Structure):
+    """fftup_device_image"""
+    _fields_ = [("data", C.c_void_p), ("format", C.c_uint32), ("row_stride_bytes", C.c_size_t), ("plane_stride_bytes", C.c_size_t)]
 
 
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
@@ -107,5 +117,13 @@ def load():
     lib.fftup_jit_check.argtypes = [u32, u32, C.c_float, u32, C.c_char_p, C.c_char_p, sz]
     lib.fftup_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, sz]
     lib.fftup_output_checksum.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
+    lib.fftup_execute_device.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp]
+    lib.fftup_device_alloc.argtypes = [C.c_int, sz]
+    lib.fftup_device_alloc.restype = vp
+    lib.fftup_device_free.argtypes = [vp]
+    lib.fftup_device_free.restype = None
+    lib.fftup_device_copy.argtypes = [vp, vp, sz, C.c_int, vp]
+    lib.fftup_stream_create.argtypes = [C.c_int, C.POINTER(vp)]
+    lib.fftup_stream_destroy.argtypes = [vp]
     _libs[path] = lib
     return lib

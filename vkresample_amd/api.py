@@ -212,6 +212,102 @@ class Upscaler:
         _check(self._lib.fftup_download_rgb8(self._h, slot, out.ctypes.data, out.strides[0]), "fftup_download_rgb8")
         return out
 
+    # ---- frames that never leave the GPU (fftup_execute_device)
+    def execute_device(self, inputs, outputs, stream=None):
+        """Run the plan on caller-owned device memory: frame i reads inputs[i] (width x height) and writes outputs[i] (out_width x
+        out_height).  `inputs` / `outputs`: one DeviceImage or a sequence of them per side; `stream`: a Stream, a raw hipStream_t
+        value or None (the default stream).  Asynchronous: the work is ordered on `stream`, nothing waits for it here.  No ring slot
+        is touched."""
+        ins = [inputs] if isinstance(inputs, DeviceImage) else list(inputs)
+        outs = [outputs] if isinstance(outputs, DeviceImage) else list(outputs)
+        if len(ins) != len(outs):
+            raise ValueError("execute_device: %d inputs, %d outputs" % (len(ins), len(outs)))
+        a = (_lib.DeviceImageDesc * len(ins))(*[i.desc() for i in ins])
+        b = (_lib.DeviceImageDesc * len(outs))(*[o.desc() for o in outs])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_execute_device(self._h, a, b, len(ins), s), "fftup_execute_device")
+
+
+class DeviceImage:
+    """One image in device memory (fftup_device_image): `ptr` an address of the plan's device, `format` FMT_RGB8 or FMT_PLANAR,
+    strides in bytes (`plane_stride` is ignored for FMT_RGB8)."""
+
+    def __init__(self, ptr, format, row_stride, plane_stride=0):
+        self.ptr, self.format, self.row_stride, self.plane_stride = ptr, format, row_stride, plane_stride
+
+    def desc(self):
+        return _lib.DeviceImageDesc(self.ptr, self.format, self.row_stride, self.plane_stride)
+
+
+class Stream:
+    """A non-blocking HIP stream of the runtime the library uses (fftup_stream_create); `.handle` is the hipStream_t."""
+
+    def __init__(self, device=0):
+        self._lib = _lib.load()
+        h = C.c_void_p()
+        _check(self._lib.fftup_stream_create(device, C.byref(h)), "fftup_stream_create")
+        self.handle = h.value
+
+    def close(self):
+        if self.handle:
+            h, self.handle = self.handle, None
+            _check(self._lib.fftup_stream_destroy(h), "fftup_stream_destroy")
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class DeviceBuffer:
+    """`nbytes` of device memory from fftup_device_alloc: what a host without HIP bindings stages frames for execute_device in.
+    upload / download are blocking copies on `stream` (a Stream or None)."""
+
+    def __init__(self, nbytes, device=0):
+        self._lib = _lib.load()
+        self.nbytes = int(nbytes)
+        self.ptr = self._lib.fftup_device_alloc(device, self.nbytes)
+        if not self.ptr:
+            raise FftupError(6, "fftup_device_alloc")
+
+    def upload(self, array, offset=0, stream=None):
+        a = np.ascontiguousarray(array)
+        assert 0 <= offset and offset + a.nbytes <= self.nbytes, (offset, a.nbytes, self.nbytes)
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_device_copy(self.ptr + offset, a.ctypes.data, a.nbytes, 0, s), "fftup_device_copy")
+
+    def download(self, nbytes=None, offset=0, stream=None):
+        nbytes = self.nbytes - offset if nbytes is None else int(nbytes)
+        assert 0 <= offset and offset + nbytes <= self.nbytes, (offset, nbytes, self.nbytes)
+        out = np.empty(nbytes, dtype=np.uint8)
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_device_copy(out.ctypes.data, self.ptr + offset, nbytes, 1, s), "fftup_device_copy")
+        return out
+
+    def close(self):
+        if self.ptr:
+            self._lib.fftup_device_free(self.ptr)
+            self.ptr = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
 
 class PinnedArray:
     """uint8 numpy view of page-locked host memory from fftup_host_alloc (needed for truly asynchronous copies

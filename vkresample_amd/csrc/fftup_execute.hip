@@ -260,7 +260,7 @@ int fftup_download_planar(fftup_plan* P, uint32_t slot, void* planes)
 int fftup_download_presharpen(fftup_plan* P, void* planes)
 {
     if (!P || !planes) return fail(FFTUP_E_INVALID_ARG, "null argument");
-    if (!P->executed) return fail(FFTUP_E_NO_INPUT, "nothing executed yet");
+    if (!P->executed && !P->dev_executed) return fail(FFTUP_E_NO_INPUT, "nothing executed yet");
     HIP_TRY(hipSetDevice(P->device));
     if (P->fused && !P->R_valid) {
         // the fused kernel never writes the pre-sharpen image; rebuild it from the spectrum of the last

@@ -20,6 +20,7 @@
 #include "kernels_downscale.hpp"
 #include "kernels_bluestein.hpp"
 #include "kernels_odd.hpp"
+#include "kernels_device_io.hpp"
 
 using namespace fftup;
 
@@ -32,6 +33,21 @@ int kernels_aot_mixed_plan(uint32_t W, uint32_t H)
     return 0;
 }
 size_t kernels_tuned_col_lds(uint32_t H) { return sizeof(float2) * (size_t)lswz_size((int)H * TUNED_TK); }   // both transforms of the column kernel have length H
+
+// where the frame being launched reads and writes: the ring slots, or what fftup_execute_device names (P->io: caller memory or
+// the lane's staging, with the caller's strides)
+static int frame_kind(const fftup_plan* P, uint32_t slot) { return P->io ? P->io->kind : P->in_kind[slot]; }
+static void* frame_out(const fftup_plan* P, uint32_t slot) { return P->io ? P->io->out : P->out[slot]; }
+template <class Q> static void set_in_u8(const fftup_plan* P, uint32_t slot, Q& q)
+{
+    if (P->io) { q.in = P->io->in; q.in_row_stride = P->io->in_row; q.in_plane_stride = 0; return; }
+    q.in = P->in_u8[slot]; q.in_row_stride = 3l * P->W; q.in_plane_stride = 0;
+}
+template <class Q> static void set_in_planar(const fftup_plan* P, uint32_t slot, Q& q)
+{
+    if (P->io) { q.in = P->io->in; q.in_row_stride = P->io->in_row; q.in_plane_stride = P->io->in_plane; return; }
+    q.in = P->in_planar[slot]; q.in_row_stride = P->W; q.in_plane_stride = (long)P->in_plane_stride;
+}
 
 // four-step rows (k_row4_a / k_row4_b): launch both passes; ATTR: only allow their dynamic LDS sizes (plan creation)
 template <typename C, int DIR, int MODE, int TKA> static hipError_t four_pass_a(const fftup_plan::Four& f, const Row4Params<C>& q, int rows, hipStream_t st, bool attr)
@@ -278,19 +294,20 @@ int kernels_set_attributes(fftup_plan* P)
 
 // ------------------------------------------------------------------------------------------------
 // the two host loops of the reference as kernels (VR:1636-1685, VR:1708-1748)
-void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st)
+void launch_unpack_from(fftup_plan* P, const uint8_t* rgb, size_t row_stride_bytes, void* planes, hipStream_t st)
 {
     dim3 grid((P->W + 255) / 256, P->H);
     if (P->dbl)
-        hipLaunchKernelGGL(k_unpack_u8_f64, grid, dim3(256), 0, st, P->in_u8[slot], (long)3 * P->W, (double*)P->in_planar[slot],
+        hipLaunchKernelGGL(k_unpack_u8_f64, grid, dim3(256), 0, st, rgb, (long)row_stride_bytes, (double*)planes,
                            (int)P->W, (int)P->H, (long)P->in_plane_stride);
     else if (P->half)
-        hipLaunchKernelGGL(k_unpack_u8<true>, grid, dim3(256), 0, st, P->in_u8[slot], (long)3 * P->W, P->in_planar[slot],
+        hipLaunchKernelGGL(k_unpack_u8<true>, grid, dim3(256), 0, st, rgb, (long)row_stride_bytes, planes,
                            (int)P->W, (int)P->H, (long)P->in_plane_stride);
     else
-        hipLaunchKernelGGL(k_unpack_u8<false>, grid, dim3(256), 0, st, P->in_u8[slot], (long)3 * P->W, P->in_planar[slot],
+        hipLaunchKernelGGL(k_unpack_u8<false>, grid, dim3(256), 0, st, rgb, (long)row_stride_bytes, planes,
                            (int)P->W, (int)P->H, (long)P->in_plane_stride);
 }
+void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st) { launch_unpack_from(P, P->in_u8[slot], (size_t)3 * P->W, P->in_planar[slot], st); }
 
 void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st)
 {
@@ -299,6 +316,31 @@ void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st)
     if (P->dbl) hipLaunchKernelGGL(k_pack_u8_f64, grid, dim3(256), 0, st, (const double*)P->out[slot], dst, (int)P->uW, (int)P->uH, wrap);
     else if (P->half) hipLaunchKernelGGL(k_pack_u8<true>, grid, dim3(256), 0, st, P->out[slot], dst, (int)P->uW, (int)P->uH, wrap);
     else hipLaunchKernelGGL(k_pack_u8<false>, grid, dim3(256), 0, st, P->out[slot], dst, (int)P->uW, (int)P->uH, wrap);
+}
+
+// fftup_execute_device: the conversion of launch_pack from a lane's scratch planes into rows of the caller's stride
+void launch_pack_to(fftup_plan* P, const void* planes, uint8_t* rgb, size_t row_stride_bytes, hipStream_t st)
+{
+    dim3 grid(P->dbl ? (P->uW + 255) / 256 : (P->uW + 1023) / 1024, P->uH);
+    const int wrap = (P->cfg.flags & FFTUP_FLAG_U8_WRAP) ? 1 : 0;
+    if (P->dbl) hipLaunchKernelGGL(k_pack_u8_f64_strided, grid, dim3(256), 0, st, (const double*)planes, rgb, (long)row_stride_bytes, (int)P->uW, (int)P->uH, wrap);
+    else if (P->half) hipLaunchKernelGGL(k_pack_u8_strided<true>, grid, dim3(256), 0, st, planes, rgb, (long)row_stride_bytes, (int)P->uW, (int)P->uH, wrap);
+    else hipLaunchKernelGGL(k_pack_u8_strided<false>, grid, dim3(256), 0, st, planes, rgb, (long)row_stride_bytes, (int)P->uW, (int)P->uH, wrap);
+}
+
+void launch_copy_rows(const void* src, size_t src_row, size_t src_plane, void* dst, size_t dst_row, size_t dst_plane,
+                      size_t row_bytes, uint32_t rows, uint32_t planes, int gran, hipStream_t st)
+{
+    CopyRowsParams p{};
+    p.src = (const uint8_t*)src; p.dst = (uint8_t*)dst; p.src_row = (long)src_row; p.src_plane = (long)src_plane;
+    p.dst_row = (long)dst_row; p.dst_plane = (long)dst_plane; p.row_bytes = (long)row_bytes;
+    const dim3 grid((unsigned)((row_bytes / 16 + 2 + 255) / 256), rows, planes);
+    switch (gran) {
+    case 8: hipLaunchKernelGGL(k_copy_rows<8>, grid, dim3(256), 0, st, p); break;
+    case 4: hipLaunchKernelGGL(k_copy_rows<4>, grid, dim3(256), 0, st, p); break;
+    case 2: hipLaunchKernelGGL(k_copy_rows<2>, grid, dim3(256), 0, st, p); break;
+    default: hipLaunchKernelGGL(k_copy_rows<1>, grid, dim3(256), 0, st, p); break;
+    }
 }
 
 // (test builds, FFTUP_EXPERIMENT planes=1: the row and column passes of the power-of-two plans on the first colour plane only --
@@ -349,7 +391,7 @@ static FusedParams fused_params(fftup_plan* P, uint32_t out_slot)
     FusedParams p{};
     p.S1 = P->lanes[P->cur].S1; p.odd_delta = (unsigned)(P->lanes[P->cur].S2 - P->lanes[P->cur].S1);
     if (P->U == 1) { p.S1 = P->lanes[P->cur].S2; p.odd_delta = 0; }      // half-integer factor: one buffer with all rows (k_col_pad)
-    p.out = P->out[out_slot]; p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
+    p.out = frame_out(P, out_slot); p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
     p.pairs_per_strip = P->pairs_per_strip; p.upsq = P->upsq; p.coef = P->coef;
     p.u8_wrap = (P->cfg.flags & FFTUP_FLAG_U8_WRAP) ? 1 : 0;
     return p;
@@ -359,13 +401,13 @@ static bool fast_sharpen_ok(const fftup_plan* P) { return !P->dbl && P->uW % 256
 
 static int launch_frame_tuned(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     if (which < 0 || which == 0) {
         RowR2CTParams p{};
         p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.H = (int)P->H; p.NT = P->NT;
         int mode;
-        if (kind == 2) { p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0; mode = P->half ? IN_U8_F16 : IN_U8_F32; }
-        else { p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride; mode = P->half ? IN_F16 : IN_F32; }
+        if (kind == 2) { set_in_u8(P, in_slot, p); mode = P->half ? IN_U8_F16 : IN_U8_F32; }
+        else { set_in_planar(P, in_slot, p); mode = P->half ? IN_F16 : IN_F32; }
         switch (P->W) {
         case 512: launch_r2c_t<512>(P, p, mode); break;
         case 1024: launch_r2c_t<1024>(P, p, mode); break;
@@ -406,7 +448,7 @@ static int launch_frame_tuned(fftup_plan* P, uint32_t in_slot, uint32_t out_slot
 static void launch_sharpen_fast(fftup_plan* P, uint32_t out_slot)
 {
     SharpenTParams p{};
-    p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
     dim3 grid(P->uW / 256, P->uH / 16, 3), block(64, 4);
     if (P->half) hipLaunchKernelGGL((k_sharpen_t<true, 4>), grid, block, 0, P->lanes[P->cur].stream, p);
     else hipLaunchKernelGGL((k_sharpen_t<false, 4>), grid, block, 0, P->lanes[P->cur].stream, p);
@@ -417,7 +459,7 @@ static void launch_sharpen(fftup_plan* P, uint32_t out_slot)
 {
     if (fast_sharpen_ok(P)) { launch_sharpen_fast(P, out_slot); return; }
     SharpenParams p{};
-    p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
     dim3 grid((P->uW + 1023) / 1024, P->uH, 3), block(256);      // (four pixels per thread; a width of 2 gave an empty grid until round 5)
     if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, P->lanes[P->cur].stream, p);
     else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, P->lanes[P->cur].stream, p);
@@ -427,17 +469,17 @@ static void launch_sharpen(fftup_plan* P, uint32_t out_slot)
 static int launch_frame_dct(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
     hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     if (which < 0 || which == 0) {
         DctRowParams p{};
         p.S1 = (float*)P->lanes[P->cur].S1; p.tw = P->twW; p.rot = P->rotW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         const dim3 grid(P->H / 2, 3), block(P->thrW);
         if (kind == 2) {
-            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            set_in_u8(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_dct_row<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_dct_row<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
         } else {
-            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            set_in_planar(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_dct_row<IN_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_dct_row<IN_F32>, grid, block, P->ldsRowF, st, p);
         }
@@ -476,14 +518,14 @@ static int launch_frame_dct(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
 static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
     hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     if (which < 0 || which == 0) {
         DownRowParams p{};
         p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         p.TK = P->TK; p.NT = P->NT; p.h = (int)P->uW / 2; p.bz = P->bzW;
         const dim3 grid(P->H / 2, 3), block(P->thrW);
-        if (kind == 2) { p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0; }
-        else { p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride; }
+        if (kind == 2) { set_in_u8(P, in_slot, p); }
+        else { set_in_planar(P, in_slot, p); }
         if (P->bzW.L) {                                      // Bluestein rows (FFTUP_FLAG_ANY_SIZE)
             if (kind == 2) {
                 if (P->half) hipLaunchKernelGGL((k_row_r2c_crop<IN_U8_F16, true>), grid, block, P->ldsRowF, st, p);
@@ -492,11 +534,11 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
             else if (P->half) hipLaunchKernelGGL((k_row_r2c_crop<IN_F16, true>), grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL((k_row_r2c_crop<IN_F32, true>), grid, block, P->ldsRowF, st, p);
         } else if (kind == 2) {
-            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            set_in_u8(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_row_r2c_crop<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
         } else {
-            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            set_in_planar(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c_crop<IN_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_row_r2c_crop<IN_F32>, grid, block, P->ldsRowF, st, p);
         }
@@ -547,7 +589,7 @@ static int launch_frame_down(fftup_plan* P, uint32_t in_slot, uint32_t out_slot,
 static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
     hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     const int kmax = (int)std::min(P->W, P->uW) / 2;
     if (which < 0 || which == 0) {
         OddRowParams p{};
@@ -555,11 +597,11 @@ static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
         p.TK = P->TK; p.NT = P->NT; p.kmax = kmax; p.fold = (P->uW < P->W && !(P->uW & 1)) ? 1 : 0; p.bz = P->bzW; p.ph = P->phW;
         const dim3 grid((P->H + 1) / 2, 3), block(P->thrW);
         if (kind == 2) {
-            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            set_in_u8(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
         } else {
-            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            set_in_planar(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_F16>, grid, block, P->ldsRowF, st, p);
             else hipLaunchKernelGGL(k_row_r2c_odd<IN_F32>, grid, block, P->ldsRowF, st, p);
         }
@@ -601,7 +643,7 @@ static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
         RowR2CParamsT<double2> p{};
         p.S1 = (double2*)P->lanes[P->cur].S1; p.tw = (const double2*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         p.TK = P->TK; p.NT = P->NT;
-        p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+        set_in_planar(P, in_slot, p);
         if (P->inplaceF) hipLaunchKernelGGL((k_row_r2c<IN_F64, double2, true>), dim3(P->H / 2, 3), dim3(P->thrW), P->ldsRowF, st, p);
         else hipLaunchKernelGGL((k_row_r2c<IN_F64, double2>), dim3(P->H / 2, 3), dim3(P->thrW), P->ldsRowF, st, p);
     }
@@ -642,7 +684,7 @@ static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
     }
     if (which < 0 || which == 3) {
         SharpenParams p{};
-        p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+        p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
         const dim3 sgrid((P->uW + 511) / 512, (P->uH + SHARPEN_F64_RPT - 1) / SHARPEN_F64_RPT, 3);
         const char* ex = fftup_jit::experiment("f64_exact_sharpen");          // (test builds: IEEE divisions and root)
         if (ex && atoi(ex)) {
@@ -677,28 +719,28 @@ template <typename C, bool HALF_OUT> static void launch_c2c_inv(fftup_plan* P, c
 template <typename C> static int launch_frame_cplx(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
     hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     using S = scalar_t<C>;
     if ((which < 0 || which == 0) && P->fourF.on) {             // rows beyond one LDS buffer: four steps through HBM
         Row4Params<C> q{};
         const fftup_plan::Four& f = P->fourF;
         q.T = (C*)P->lanes[P->cur].T4; q.S1 = (C*)P->lanes[P->cur].S1; q.tw1 = (const C*)f.tw1; q.tw2 = (const C*)f.tw2; q.twN = (const C*)P->twW;
         q.plan1 = f.p1; q.plan2 = f.p2; q.N = (int)P->W; q.N1 = f.n1; q.N2 = f.n2; q.rows = (int)P->H; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT;
-        if (kind == 2) { q.in = P->in_u8[in_slot]; q.in_row_stride = 3l * P->W; q.in_plane_stride = 0; }
-        else { q.in = P->in_planar[in_slot]; q.in_row_stride = P->W; q.in_plane_stride = (long)P->in_plane_stride; }
+        if (kind == 2) { set_in_u8(P, in_slot, q); }
+        else { set_in_planar(P, in_slot, q); }
         (void)four_forward<C, false>(P, q, kind, st);
     } else if (which < 0 || which == 0) {
         RowR2CParamsT<C> p{};
         p.S1 = (C*)P->lanes[P->cur].S1; p.tw = (const C*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         p.TK = P->TK; p.NT = P->NT;
         if (kind == 2) {
-            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            set_in_u8(P, in_slot, p);
             if constexpr (sizeof(S) == 4) {
                 if (P->half) launch_c2c_fwd<C, IN_U8_F16>(P, p, st);
                 else launch_c2c_fwd<C, IN_U8_F32>(P, p, st);
             }
         } else {
-            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            set_in_planar(P, in_slot, p);
             if constexpr (sizeof(S) == 8) launch_c2c_fwd<C, IN_F64>(P, p, st);
             else if (P->half) launch_c2c_fwd<C, IN_F16>(P, p, st);
             else launch_c2c_fwd<C, IN_F32>(P, p, st);
@@ -742,7 +784,7 @@ template <typename C> static int launch_frame_cplx(fftup_plan* P, uint32_t in_sl
     }
     if (which < 0 || which == 3) {
         SharpenParams p{};
-        p.R = P->lanes[P->cur].R; p.out = P->out[out_slot]; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+        p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
         bool done = false;
         if constexpr (sizeof(S) == 4) {
             if (P->half) { hipLaunchKernelGGL((k_sharpen_c<C, true>), dim3((P->uW + 255) / 256, P->uH, 3), dim3(256), 0, st, p); done = true; }
@@ -760,8 +802,8 @@ template <class CFG> static void launch_row_mixed(fftup_plan* P, uint32_t in_slo
     RowR2CTParams q{};
     q.S1 = P->lanes[P->cur].S1; q.tw = P->twW; q.H = (int)P->H; q.NT = P->NT;
     int mode;
-    if (kind == 2) { q.in = P->in_u8[in_slot]; q.in_row_stride = 3l * P->W; q.in_plane_stride = 0; mode = P->half ? IN_U8_F16 : IN_U8_F32; }
-    else { q.in = P->in_planar[in_slot]; q.in_row_stride = P->W; q.in_plane_stride = (long)P->in_plane_stride; mode = P->half ? IN_F16 : IN_F32; }
+    if (kind == 2) { set_in_u8(P, in_slot, q); mode = P->half ? IN_U8_F16 : IN_U8_F32; }
+    else { set_in_planar(P, in_slot, q); mode = P->half ? IN_F16 : IN_F32; }
     hipStream_t st = P->lanes[P->cur].stream;
     const dim3 grid(P->H / 2, 3), block(CFG::ROW_T);
     switch (mode) {
@@ -782,7 +824,7 @@ static void keep_first(hipError_t& first, hipError_t e) { if (first == hipSucces
 
 int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
-    const int kind = P->in_kind[in_slot];
+    const int kind = frame_kind(P, in_slot);
     if (kind == 0 && which != 22) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (22, the pre-sharpen tap, reads spectra only)
     if (P->cplx) return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
     if (P->dbl) return launch_frame_f64(P, in_slot, out_slot, which);
@@ -805,8 +847,8 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
         if (P->mixed == 3 && P->jit->choice.row_kind != 2) {
             RowR2CTParams q{};
             q.S1 = P->lanes[P->cur].S1; q.tw = P->twW; q.H = (int)P->H; q.NT = P->NT;
-            if (kind == 2) { q.in = P->in_u8[in_slot]; q.in_row_stride = 3l * P->W; q.in_plane_stride = 0; }
-            else { q.in = P->in_planar[in_slot]; q.in_row_stride = P->W; q.in_plane_stride = (long)P->in_plane_stride; }
+            if (kind == 2) { set_in_u8(P, in_slot, q); }
+            else { set_in_planar(P, in_slot, q); }
             keep_first(jerr, fftup_jit::launch(P->jit->fn[kind == 2 ? fftup_jit::K_ROW_U8 : fftup_jit::K_ROW_PLANAR], grid, dim3(P->jit->choice.row_block), 0,
                                      P->lanes[P->cur].stream, q));
         } else if (P->mixed == 1 || P->mixed == 2) {
@@ -814,20 +856,20 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
         } else if (P->bzW.L) {                               // Bluestein rows (FFTUP_FLAG_ANY_SIZE)
             hipStream_t st = P->lanes[P->cur].stream;
             if (kind == 2) {
-                p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+                set_in_u8(P, in_slot, p);
                 if (P->half) hipLaunchKernelGGL(k_row_r2c_bz<IN_U8_F16>, grid, block, P->ldsRowF, st, p, P->bzW);
                 else hipLaunchKernelGGL(k_row_r2c_bz<IN_U8_F32>, grid, block, P->ldsRowF, st, p, P->bzW);
             } else {
-                p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+                set_in_planar(P, in_slot, p);
                 if (P->half) hipLaunchKernelGGL(k_row_r2c_bz<IN_F16>, grid, block, P->ldsRowF, st, p, P->bzW);
                 else hipLaunchKernelGGL(k_row_r2c_bz<IN_F32>, grid, block, P->ldsRowF, st, p, P->bzW);
             }
         } else if (kind == 2) {
-            p.in = P->in_u8[in_slot]; p.in_row_stride = 3l * P->W; p.in_plane_stride = 0;
+            set_in_u8(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c<IN_U8_F16>, grid, block, P->ldsRowF, P->lanes[P->cur].stream, p);
             else hipLaunchKernelGGL(k_row_r2c<IN_U8_F32>, grid, block, P->ldsRowF, P->lanes[P->cur].stream, p);
         } else {
-            p.in = P->in_planar[in_slot]; p.in_row_stride = P->W; p.in_plane_stride = (long)P->in_plane_stride;
+            set_in_planar(P, in_slot, p);
             if (P->half) hipLaunchKernelGGL(k_row_r2c<IN_F16>, grid, block, P->ldsRowF, P->lanes[P->cur].stream, p);
             else hipLaunchKernelGGL(k_row_r2c<IN_F32>, grid, block, P->ldsRowF, P->lanes[P->cur].stream, p);
         }

@@ -374,6 +374,8 @@ void fftup_plan_destroy(fftup_plan* P)
         if (qs.png.parts_host) (void)hipHostFree(qs.png.parts_host);
     }
     if (P->png_copy) (void)hipStreamDestroy(P->png_copy);
+    if (P->dio.start) (void)hipEventDestroy(P->dio.start);
+    for (hipEvent_t e : P->dio.done) if (e) (void)hipEventDestroy(e);
     for (void* p : P->allocs) (void)hipFree(p);
     delete P->jit;
     if (P->ev0) (void)hipEventDestroy(P->ev0);

@@ -5,6 +5,7 @@
 //   fftup_execute.hip  upload / execute / download (performVulkanUpscale, VkResample.cpp:1249-1279, and the transfers)
 //   fftup_queue.hip    host-streamed frames: fftup_submit_rgb8 / fftup_wait / fftup_drain
 //   fftup_png.hip      the device-side PNG encoder's host side
+//   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device and the device / stream helpers
 //   jit.cpp            the plan-time compiler
 #pragma once
 #include <hip/hip_runtime.h>
@@ -147,6 +148,16 @@ struct fftup_plan {
     size_t in_plane_stride = 0;
     int executed = 0;
 
+    // fftup_execute_device: while `io` is set the frame being launched reads `in` (kind 1: planes, strides in elements; kind 2:
+    // 8-bit RGB, row stride in bytes) and its last kernel writes `out` -- caller memory or the lane's staging -- instead of ring slots
+    struct FrameIO { const void* in = nullptr; int kind = 0; long in_row = 0, in_plane = 0; void* out = nullptr; };
+    const FrameIO* io = nullptr;
+    // created by the first call that needs them: one start event, one completion event per lane; per lane the staging planes
+    // (the in_planar layout) and the scratch image (the layout of an output slot) of the layouts that cannot run in place
+    struct DeviceIO { hipEvent_t start = nullptr; std::vector<hipEvent_t> done; std::vector<void*> stage_in, scratch_out; };
+    DeviceIO dio;
+    bool dev_executed = false;        // a frame of fftup_execute_device has run: the pre-sharpen tap is valid, the slots are not
+
     std::vector<void*> allocs;
 };
 
@@ -174,6 +185,13 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which);
 void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st);                  // the host loop of VR:1636-1685 as a kernel
 void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st);      // ... and of VR:1708-1748
 void launch_checksum(fftup_plan* P, uint32_t slot, hipStream_t st);                // 64-bit sum of the slot's words -> P->d_sum
+// frames in caller-owned device memory (kernels_device_io.hpp)
+void launch_unpack_from(fftup_plan* P, const uint8_t* rgb, size_t row_stride_bytes, void* planes, hipStream_t st);   // -> the in_planar layout
+void launch_pack_to(fftup_plan* P, const void* planes, uint8_t* rgb, size_t row_stride_bytes, hipStream_t st);     // dense planes -> rows of row_stride_bytes
+// `planes` x `rows` rows of row_bytes bytes between two strided layouts (strides in bytes); gran: 1, 2, 4 or 8, a power of two
+// that divides both addresses, all four strides and row_bytes
+void launch_copy_rows(const void* src, size_t src_row, size_t src_plane, void* dst, size_t dst_row, size_t dst_plane,
+                      size_t row_bytes, uint32_t rows, uint32_t planes, int gran, hipStream_t st);
 
 // ---- fftup_execute.hip
 int execute_ring_impl(fftup_plan* P, uint32_t n_frames, uint32_t first_slot, double* ms_total, double* kernel_ms, uint32_t stride);
