@@ -256,6 +256,41 @@ FFTUP_API int fftup_plan_create(fftup_plan** out, const fftup_config* cfg);
 enum { FFTUP_ALIGN_CORNER = 0, FFTUP_ALIGN_CENTRE = 1 };
 FFTUP_API int fftup_plan_create_size(fftup_plan** out, const fftup_config* cfg,
                                      uint32_t out_width, uint32_t out_height, uint32_t align);
+/* EXTENSION: a VIEW plan -- zoom into a region, pan by a fraction of a pixel, scale by any real ratio.  The out_width x out_height
+ * output shows the rectangle of the frame that starts at input position (origin_x, origin_y) and is (span_x, span_y) input pixels
+ * wide and high: per axis N -> M with step s = span / M, output pixel m sits at input position t_m = origin + m s (pixel indices as
+ * coordinates, the frame periodic with period N).  The plan evaluates the frame's trigonometric interpolant there, separably:
+ * with X[f] = sum_n x[n] exp(-2 pi i nf / N),
+ *   kmax = min(N/2 (integer division), floor((double)(N M) / (2 max(span, (double)M)))),   g_f = 1/2 if 2 |f| == N, else 1,
+ *   y[m] = (1/N) sum_{f = -kmax .. kmax} g_f X[f mod N] exp(2 pi i f t_m / N).
+ * For s <= 1 this is the full interpolant (an even N's Nyquist bin enters as X[N/2] cos(pi t)); for s > 1 the spectrum is truncated
+ * at the output's Nyquist frequency: no aliasing.  It interpolates the WHOLE frame, so an interior view has no seam (cropping first
+ * would make the crop periodic).  origin = 0, span = N is fftup_plan_create_size with FFTUP_ALIGN_CORNER, origin = (N/M - 1)/2 with
+ * FFTUP_ALIGN_CENTRE (the fold, split and kept rules of FFTUP_FLAG_ODD_SIZE follow from kmax and g).  A rectangle given in
+ * pixel-EDGE coordinates [x0, x0 + w) with the centres aligned is origin = x0 + w/(2M) - 1/2, span = w.
+ * The pre-sharpen image is R = y span_x span_y / (uW uH); the sharpen pass is the existing one, unchanged (quirks B4, B5), with the
+ * effective factor u_e = (float)sqrt((double)uW uH / (span_x span_y)) in the place of cfg->upscale: upsq = "%f"(u_e u_e), the product
+ * formed in fp32.
+ * cfg->upscale is ignored; every other field means what it means for fftup_plan_create_size, and the plan is an ordinary plan: upload,
+ * execute, ring, submit, PNG, download, checksum, fftup_execute_device, info and describe work on it unchanged.  FFTUP_FLAG_ODD_SIZE and
+ * FFTUP_FLAG_DOWNSCALE are implied; FFTUP_FLAG_ANY_SIZE keeps its meaning and matters for width and height only (the forward
+ * transforms are the only ones of the input's lengths; out_width and out_height may be any numbers).
+ * Each axis runs as a chirp-z transform: a cyclic convolution of a 2,3,5,7-smooth length L >= 2 (N/2) + M, fixed by N and M.  Four
+ * launches (fftup_info.tuned = u8_store = 0; kernel names row_r2c_odd[_bz], col_view[_bz], row_view_c2r, sharpen).
+ * Bounds (arithmetic, decided before any device access; fftup_last_error names the rule): FFTUP_E_INVALID_ARG for null pointers,
+ * channels != 3, a length below 2, a non-finite origin or span, a step span / M outside [1/64, 8] on either axis;
+ * FFTUP_E_UNSUPPORTED_PRECISION for -p 1; FFTUP_E_UNSUPPORTED_SIZE with FFTUP_FLAG_DCT, for width > 8192, for a row convolution length
+ * above 8192, for a width or height with a prime factor above 7 without FFTUP_FLAG_ANY_SIZE or above 4096, and for columns whose two
+ * local-memory buffers do not fit at a tile width of 1.  fftup_version() is unchanged: detect the mode by this symbol.
+ *
+ * fftup_plan_set_view re-aims a view plan without re-creating it (a pan or a zoom per frame): it waits for the plan's own streams,
+ * rebuilds the host tables and uploads them -- blocking; frames executed afterwards show the new view.  Everything is sized for the
+ * worst case of the plan's four lengths at creation, so every valid view fits.  FFTUP_E_INVALID_ARG: a null pointer, a plan that is
+ * not a view plan, a non-finite value, a step outside [1/64, 8]; the plan then keeps its view. */
+typedef struct fftup_view { double origin_x, origin_y, span_x, span_y; } fftup_view;
+FFTUP_API int fftup_plan_create_view(fftup_plan** out, const fftup_config* cfg,
+                                     uint32_t out_width, uint32_t out_height, const fftup_view* view);
+FFTUP_API int fftup_plan_set_view(fftup_plan* plan, const fftup_view* view);
 /* deleteVulkanFFT x2, deleteShiftApp x2, buffer frees (VR:1759-1771) */
 FFTUP_API void fftup_plan_destroy(fftup_plan* plan);
 FFTUP_API int fftup_plan_info(const fftup_plan* plan, fftup_info* info);

@@ -38,7 +38,7 @@ EXPORTS = [
     "fftup_drain", "fftup_strerror", "fftup_last_error", "fftup_version", "fftup_jit_check", "fftup_plan_describe",
     "fftup_device_pci_bus_id", "fftup_output_checksum", "fftup_png_bound", "fftup_submit_png", "fftup_wait_png",
     "fftup_plan_create_size", "fftup_execute_device", "fftup_device_alloc", "fftup_device_free", "fftup_device_copy",
-    "fftup_stream_create", "fftup_stream_destroy",
+    "fftup_stream_create", "fftup_stream_destroy", "fftup_plan_create_view", "fftup_plan_set_view",
 ]
 ABI_VERSION = 2
 
@@ -63,6 +63,11 @@ class DeviceImageDesc(C.Structure):
     _fields_ = [("data", C.c_void_p), ("format", C.c_uint32), ("row_stride_bytes", C.c_size_t), ("plane_stride_bytes", C.c_size_t)]
 
 
+class View(C.Structure):
+    """fftup_view: the rectangle of the frame a view plan shows, origin and span per axis in input pixels"""
+    _fields_ = [("origin_x", C.c_double), ("origin_y", C.c_double), ("span_x", C.c_double), ("span_y", C.c_double)]
+
+
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
 _libs = {}
 
@@ -84,6 +89,8 @@ def load():
     lib.fftup_device_name.argtypes = [C.c_int, C.c_char_p, sz]
     lib.fftup_plan_create.argtypes = [C.POINTER(vp), C.POINTER(Config)]
     lib.fftup_plan_create_size.argtypes = [C.POINTER(vp), C.POINTER(Config), u32, u32, u32]
+    lib.fftup_plan_create_view.argtypes = [C.POINTER(vp), C.POINTER(Config), u32, u32, C.POINTER(View)]
+    lib.fftup_plan_set_view.argtypes = [vp, C.POINTER(View)]
     lib.fftup_plan_destroy.argtypes = [vp]
     lib.fftup_plan_destroy.restype = None
     lib.fftup_plan_info.argtypes = [vp, C.POINTER(Info)]

@@ -59,11 +59,37 @@ class Upscaler:
         self._create(width, height, 1.0, precision, sharpen, device, flags, ring, (out_width, out_height, align))
         return self
 
-    def _create(self, width, height, upscale, precision, sharpen, device, flags, ring, size):
+    @classmethod
+    def view(cls, width, height, out_width, out_height, origin, span, precision=0, sharpen=0.2, device=0, flags=0, ring=1):
+        """A view plan (fftup_plan_create_view): the out_width x out_height output shows the rectangle of the frame that starts at
+        input position origin = (x, y) and is span = (w, h) input pixels wide and high -- output pixel m of an axis at origin + m span / M,
+        any real numbers (zoom, sub-pixel pan, any ratio; the frame is periodic).  view_of_rect gives (origin, span) of a rectangle in
+        pixel-edge coordinates.  set_view re-aims the plan."""
+        self = cls.__new__(cls)
+        self._create(width, height, 1.0, precision, sharpen, device, flags, ring, (out_width, out_height), (origin, span))
+        return self
+
+    def set_view(self, origin, span):
+        """Re-aim a view plan (fftup_plan_set_view): blocking, no plan creation; frames executed afterwards show the new view."""
+        v = _lib.View(origin[0], origin[1], span[0], span[1])
+        _check(self._lib.fftup_plan_set_view(self._h, C.byref(v)), "fftup_plan_set_view")
+        buf = C.create_string_buffer(512)
+        _check(self._lib.fftup_plan_describe(self._h, buf, 512), "fftup_plan_describe")
+        self.description = buf.value.decode()
+        info = _lib.Info()
+        _check(self._lib.fftup_plan_info(self._h, C.byref(info)), "fftup_plan_info")
+        self.alg_bytes_per_frame = info.alg_bytes_per_frame
+        self.kernel_alg_bytes = list(info.kernel_alg_bytes)
+        self.kernel_min_bytes = list(info.kernel_min_bytes)
+
+    def _create(self, width, height, upscale, precision, sharpen, device, flags, ring, size, view=None):
         self._lib = _lib.load()
         self._h = C.c_void_p()
         cfg = _lib.Config(width, height, 3, upscale, precision, sharpen, device, flags, ring)
-        if size is None:
+        if view is not None:
+            v = _lib.View(view[0][0], view[0][1], view[1][0], view[1][1])
+            _check(self._lib.fftup_plan_create_view(C.byref(self._h), C.byref(cfg), size[0], size[1], C.byref(v)), "fftup_plan_create_view")
+        elif size is None:
             _check(self._lib.fftup_plan_create(C.byref(self._h), C.byref(cfg)), "fftup_plan_create")
         else:
             _check(self._lib.fftup_plan_create_size(C.byref(self._h), C.byref(cfg), size[0], size[1], size[2]), "fftup_plan_create_size")
@@ -338,6 +364,12 @@ class PinnedArray:
             self.close()
         except Exception:
             pass
+
+
+def view_of_rect(x0, y0, w, h, out_width, out_height):
+    """(origin, span) of Upscaler.view for the rectangle [x0, x0 + w) x [y0, y0 + h) in pixel-EDGE coordinates (pixel n covers
+    [n, n + 1)), pixel centres aligned: per axis origin = x0 + w / (2 M) - 1/2, span = w."""
+    return ((x0 + w / (2.0 * out_width) - 0.5, y0 + h / (2.0 * out_height) - 0.5), (float(w), float(h)))
 
 
 def upscale_image(rgb, upscale=2.0, precision=0, sharpen=0.2, num_iter=1, device=0, flags=0):

@@ -21,6 +21,8 @@
 //   -downscale    FFTUP_FLAG_DOWNSCALE: -u in [1/8, 1) crops the spectrum (band-limited decimation; with -dct: truncated DCT)
 //   -size WxH     fftup_plan_create_size: the exact output size instead of -u, one factor per axis (each axis up, down or equal)
 //   -centres      with -size: pixel centres aligned (FFTUP_ALIGN_CENTRE) instead of pixel 0 on pixel 0
+//   -view ox,oy,sx,sy  with -size: fftup_plan_create_view -- the output shows the rectangle of the frame that starts at input position
+//                 (ox, oy) and spans (sx, sy) input pixels: zoom, sub-pixel pan, any real ratio (the frame is periodic)
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -59,11 +61,14 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     bool gpuPng = false;                     // -gpupng: batched mode: the GPU delivers the finished PNG (fftup_submit_png)
     uint32_t outWidth = 0, outHeight = 0;    // -size WxH (0: none, the output size follows from -u)
     uint32_t align = FFTUP_ALIGN_CORNER;     // -centres
+    bool hasView = false;                    // -view ox,oy,sx,sy (with -size)
+    fftup_view view{};
 };
 
-// fftup_plan_create, or fftup_plan_create_size under -size
+// fftup_plan_create, fftup_plan_create_size under -size, fftup_plan_create_view under -size with -view
 static int create_plan(const ResampleConfiguration& config, fftup_plan** plan, const fftup_config& cfg)
 {
+    if (config.hasView) return fftup_plan_create_view(plan, &cfg, config.outWidth, config.outHeight, &config.view);
     if (config.outWidth) return fftup_plan_create_size(plan, &cfg, config.outWidth, config.outHeight, config.align);
     return fftup_plan_create(plan, &cfg);
 }
@@ -302,7 +307,10 @@ static int launchResample(ResampleConfiguration config)                      // 
             fftup_plan_destroy(plan);
             return res;
         }
-        if (!config.fileUpload && config.outWidth)
+        if (!config.fileUpload && config.hasView)
+            printf("VkResample view %g,%g+%gx%g: %dx%d to %dx%d Time: %0.3f ms\n", config.view.origin_x, config.view.origin_y, config.view.span_x, config.view.span_y,
+                   width, height, uW, uH, totTime);
+        else if (!config.fileUpload && config.outWidth)
             printf("VkResample exact size%s: %dx%d to %dx%d Time: %0.3f ms\n", config.align == FFTUP_ALIGN_CENTRE ? " (centres)" : "", width, height, uW, uH, totTime);
         else if (!config.fileUpload)
             printf("VkResample %0.1fx upscale: %dx%d to %dx%d Time: %0.3f ms\n", config.upscale, width, height, uW, uH, totTime);   // VR:1694
@@ -365,6 +373,7 @@ int main(int argc, char* argv[])
         printf("	-downscale: allow -u in [1/8, 1), e.g. -u 1/2: spectral downscale (band-limited, no aliasing; -p 0 and -p 2; with -dct: DCT downscale)\n");
         printf("	-size WxH: the exact output size instead of -u, e.g. -size 1920x1080 on 1366x768: one factor per axis, each between 1/8 and 8, up or down (exact trigonometric resampling; -p 0 and -p 2, not with -dct or -u; -anysize for lengths with prime factors above 7)\n");
         printf("	-centres: with -size: align the pixel centres, as other resizers do (default: output pixel 0 on input pixel 0)\n");
+        printf("	-view OX,OY,SX,SY: with -size: show the rectangle of the image that starts at position (OX, OY) and spans SX x SY input pixels, e.g. -size 1920x1080 -view 480,270,960,540 on 1920x1080: a 2x zoom about the centre; any real numbers (sub-pixel pan, any ratio; the image is periodic; a step SX/W outside [1/64, 8] is refused; not with -centres)\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -398,6 +407,18 @@ int main(int argc, char* argv[])
             return 1;
         }
         if (findFlag(B, E, "-centres")) config.align = FFTUP_ALIGN_CENTRE;
+        if (findFlag(B, E, "-view")) {
+            char* w = getFlagValue(B, E, "-view");
+            if (config.align == FFTUP_ALIGN_CENTRE) { printf("-view places the output pixels itself: it cannot be combined with -centres\n"); return 1; }
+            if (!w || sscanf(w, "%lf,%lf,%lf,%lf%c", &config.view.origin_x, &config.view.origin_y, &config.view.span_x, &config.view.span_y, &tail) != 4) {
+                printf("No proper view is selected with -view flag (OX,OY,SX,SY, e.g. 480,270,960,540)\n");
+                return 1;
+            }
+            config.hasView = true;
+        }
+    } else if (findFlag(B, E, "-view")) {
+        printf("-view needs an output size given with -size\n");
+        return 1;
     } else if (findFlag(B, E, "-centres")) {
         printf("-centres needs an output size given with -size\n");
         return 1;

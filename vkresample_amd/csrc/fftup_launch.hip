@@ -20,6 +20,7 @@
 #include "kernels_downscale.hpp"
 #include "kernels_bluestein.hpp"
 #include "kernels_odd.hpp"
+#include "kernels_view.hpp"
 #include "kernels_device_io.hpp"
 
 using namespace fftup;
@@ -130,6 +131,17 @@ int kernels_set_attributes(fftup_plan* P)
             case 4: SET_LDS(k_dct_col<4>, P->ldsCol); break;
             case 2: SET_LDS(k_dct_col<2>, P->ldsCol); break;
             default: SET_LDS(k_dct_col<1>, P->ldsCol); break;
+            }
+            return FFTUP_OK;
+        }
+        if (P->view) {                                       // (fftup_plan_create_view: kernels_view.hpp + the odd-size plans' row R2C)
+            if (P->half) { SET_LDS(k_row_r2c_odd<IN_F16>, P->ldsRowF); SET_LDS(k_row_r2c_odd<IN_U8_F16>, P->ldsRowF); SET_LDS(k_row_view_c2r<true>, P->ldsRowI); }
+            else { SET_LDS(k_row_r2c_odd<IN_F32>, P->ldsRowF); SET_LDS(k_row_r2c_odd<IN_U8_F32>, P->ldsRowF); SET_LDS(k_row_view_c2r<false>, P->ldsRowI); }
+            switch (P->TK) {
+            case 8: SET_LDS(k_col_view<8>, P->ldsCol); break;
+            case 4: SET_LDS(k_col_view<4>, P->ldsCol); break;
+            case 2: SET_LDS(k_col_view<2>, P->ldsCol); break;
+            default: SET_LDS(k_col_view<1>, P->ldsCol); break;
             }
             return FFTUP_OK;
         }
@@ -635,6 +647,60 @@ static int launch_frame_odd(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, 
     return FFTUP_OK;
 }
 
+// fftup_plan_create_view: row R2C keeping kx <= kmax_x (the odd-size plans' kernel: no fold, no phase table) -> column forward /
+// signed bins / chirp-z to uH points -> two spectrum rows / chirp-z to uW points -> sharpen (kernels_view.hpp)
+static CztPlan czt_plan(const fftup_plan::ViewAxis& a, uint32_t M)
+{
+    CztPlan z{};
+    z.L = (int32_t)a.L; z.K = 2 * a.kmax + 1; z.M = (int32_t)M; z.plan = a.planL; z.tw = a.tw; z.pre = a.pre; z.post = a.post; z.bhat = a.bhat;
+    return z;
+}
+static int launch_frame_view(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+{
+    hipStream_t st = P->lanes[P->cur].stream;
+    const int kind = frame_kind(P, in_slot);
+    if (which < 0 || which == 0) {
+        OddRowParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.fold = 0; p.bz = P->bzW; p.ph = nullptr;
+        const dim3 grid((P->H + 1) / 2, 3), block(P->thrW);
+        if (kind == 2) {
+            set_in_u8(P, in_slot, p);
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_odd<IN_U8_F32>, grid, block, P->ldsRowF, st, p);
+        } else {
+            set_in_planar(P, in_slot, p);
+            if (P->half) hipLaunchKernelGGL(k_row_r2c_odd<IN_F16>, grid, block, P->ldsRowF, st, p);
+            else hipLaunchKernelGGL(k_row_r2c_odd<IN_F32>, grid, block, P->ldsRowF, st, p);
+        }
+    }
+    if (which < 0 || which == 1) {
+        ViewColParams p{};
+        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.planH = P->planH;
+        p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.kmax = P->vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, P->uH);
+        const dim3 grid(P->NT, 3), block(P->thrCol);
+        switch (P->TK) {
+        case 8: hipLaunchKernelGGL(k_col_view<8>, grid, block, P->ldsCol, st, p); break;
+        case 4: hipLaunchKernelGGL(k_col_view<4>, grid, block, P->ldsCol, st, p); break;
+        case 2: hipLaunchKernelGGL(k_col_view<2>, grid, block, P->ldsCol, st, p); break;
+        default: hipLaunchKernelGGL(k_col_view<1>, grid, block, P->ldsCol, st, p); break;
+        }
+    }
+    if (which < 0 || which == 2) {
+        ViewC2RParams p{};
+        p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.uW = (int)P->uW; p.uH = (int)P->uH;
+        p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.z = czt_plan(P->vx, P->uW);
+        const dim3 grid((P->uH + 1) / 2, 3), block(P->thrUW);
+        if (P->half) hipLaunchKernelGGL(k_row_view_c2r<true>, grid, block, P->ldsRowI, st, p);
+        else hipLaunchKernelGGL(k_row_view_c2r<false>, grid, block, P->ldsRowI, st, p);
+        P->R_valid = true;
+    }
+    if (which < 0 || which == 3) launch_sharpen(P, out_slot);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
+    return FFTUP_OK;
+}
+
 // -p 1: the size-generic kernels instantiated on double2 + the double sharpen
 static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
 {
@@ -829,6 +895,7 @@ int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
     if (P->cplx) return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
     if (P->dbl) return launch_frame_f64(P, in_slot, out_slot, which);
     if (P->dct) return launch_frame_dct(P, in_slot, out_slot, which);
+    if (P->view) return launch_frame_view(P, in_slot, out_slot, which);
     if (P->odd) return launch_frame_odd(P, in_slot, out_slot, which);
     if (P->down) return launch_frame_down(P, in_slot, out_slot, which);
     if (P->tuned) {

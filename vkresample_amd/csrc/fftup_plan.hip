@@ -15,6 +15,7 @@
 #include <hip/hip_fp16.h>
 
 #include "plan.hpp"
+#include "view_tables.hpp"
 
 using namespace fftup;
 
@@ -159,24 +160,7 @@ static int bluestein_col_tk(uint32_t H, uint32_t uH)
         if (lds_length(H, tk) && lds_length(uH, tk)) return tk;
     return 0;
 }
-// DFT with exp(+2 pi i nk / n) of a smooth length in double (recursive decimation in time by the smallest prime factor)
-static void host_fft(std::vector<std::complex<double>>& x)
-{
-    const size_t n = x.size();
-    if (n <= 1) return;
-    size_t p = 2;
-    while (n % p) p++;
-    const size_t m = n / p;
-    std::vector<std::vector<std::complex<double>>> sub(p, std::vector<std::complex<double>>(m));
-    for (size_t j = 0; j < m; j++)
-        for (size_t r = 0; r < p; r++) sub[r][j] = x[j * p + r];
-    for (auto& v : sub) host_fft(v);
-    for (size_t k = 0; k < n; k++) {
-        std::complex<double> acc = sub[0][k % m];
-        for (size_t r = 1; r < p; r++) acc += sub[r][k % m] * std::polar(1.0, 2.0 * M_PI * (double)((r * k) % n) / (double)n);
-        x[k] = acc;
-    }
-}
+using fftup_viewtab::host_fft;                   // DFT with exp(+2 pi i nk / n) of a smooth length in double (view_tables.hpp)
 // the tables of one Bluestein transform of n points through length L, in double, rounded once to fp32 (as make_twiddles).  The
 // phase pi k^2 / n is reduced as (k^2 mod 2n) in 64-bit integers BEFORE the division: it reaches thousands of radians.
 static int make_bluestein(fftup_plan* P, BzPlan* z, uint32_t n, uint32_t L, const StagePlan& planL)
@@ -422,9 +406,57 @@ static int make_phases(fftup_plan* P, float2** dptr, uint32_t N, uint32_t M)
     return FFTUP_OK;
 }
 
-// fftup_plan_create (size == nullptr: the output size follows from cfg->upscale) and fftup_plan_create_size (size = {uW, uH},
-// cfg->upscale ignored)
-static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint32_t* size, uint32_t align)
+// ---- fftup_plan_create_view (kernels_view.hpp, view_tables.hpp)
+// the rules of one view, shared by plan creation and fftup_plan_set_view (arithmetic only)
+static int check_view(const char* who, const fftup_view* v, uint32_t uW, uint32_t uH)
+{
+    if (!std::isfinite(v->origin_x) || !std::isfinite(v->origin_y) || !std::isfinite(v->span_x) || !std::isfinite(v->span_y))
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": origin and span must be finite numbers");
+    const double sx = v->span_x / (double)uW, sy = v->span_y / (double)uH;
+    if (!(sx >= 1.0 / 64 && sx <= 8.0)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": the step span_x / out_width must lie in [1/64, 8]");
+    if (!(sy >= 1.0 / 64 && sy <= 8.0)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": the step span_y / out_height must lie in [1/64, 8]");
+    return FFTUP_OK;
+}
+// column tile width of a view plan: the widest of 8, 4, 2, 1 at which max(H, its Bluestein length, L_y) * TK fits twice; 0: none
+static int view_col_tk(uint32_t H, uint32_t uH)
+{
+    const uint32_t Ly = fftup_viewtab::conv_length(H, uH);
+    for (int tk : {8, 4, 2, 1})
+        if (lds_length(H, tk) && two_buffers_fit((size_t)std::max(lds_length(H, tk), Ly) * tk)) return tk;
+    return 0;
+}
+static float view_factor(const fftup_view& v, uint32_t uW, uint32_t uH)
+{
+    return (float)std::sqrt((double)uW * (double)uH / (v.span_x * v.span_y));
+}
+// Aim the plan at `v`: kmax per axis, the spectrum columns kept, the sharpen constant, the tables (blocking copies; the caller has
+// made sure nothing of the plan is running).  An axis whose span did not change keeps its chirp tables: only `pre` holds the origin.
+static int view_apply(fftup_plan* P, const fftup_view& v, bool first)
+{
+    struct Ax { fftup_plan::ViewAxis* a; uint32_t N, M; double o, sp, sp_old; };
+    const Ax ax[2] = {{&P->vx, P->W, P->uW, v.origin_x, v.span_x, P->vw.span_x}, {&P->vy, P->H, P->uH, v.origin_y, v.span_y, P->vw.span_y}};
+    for (const Ax& x : ax) {
+        fftup_viewtab::AxisTables t;
+        const bool chirp = first || x.sp != x.sp_old;
+        fftup_viewtab::make_axis(x.N, x.M, x.o, x.sp, x.a->L, t, chirp);
+        x.a->kmax = t.kmax;
+        HIP_TRY(hipMemcpy(x.a->pre, t.pre.data(), sizeof(float) * t.pre.size(), hipMemcpyHostToDevice));
+        if (chirp) {
+            HIP_TRY(hipMemcpy(x.a->post, t.post.data(), sizeof(float) * t.post.size(), hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(x.a->bhat, t.bhat.data(), sizeof(float) * t.bhat.size(), hipMemcpyHostToDevice));
+        }
+    }
+    P->vw = v;
+    P->ncols = P->vx.kmax + 1;
+    P->NT = (P->ncols + P->TK - 1) / P->TK;
+    P->cfg.upscale = view_factor(v, P->uW, P->uH);
+    P->upsq = const_via_percent_f((double)(P->cfg.upscale * P->cfg.upscale), P->half);
+    return FFTUP_OK;
+}
+
+// fftup_plan_create (size == nullptr: the output size follows from cfg->upscale), fftup_plan_create_size (size = {uW, uH},
+// cfg->upscale ignored) and fftup_plan_create_view (size and view)
+static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint32_t* size, uint32_t align, const fftup_view* view = nullptr)
 {
     if (!out || !cfg_in) return fail(FFTUP_E_INVALID_ARG, "null argument");
     *out = nullptr;
@@ -450,7 +482,27 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
     if (!(cfg->sharpen == cfg->sharpen)) return fail(FFTUP_E_INVALID_ARG, "sharpen is NaN");
     const uint32_t uW = exact ? size[0] : (uint32_t)(cfg->upscale * (float)W);     // VkResample.cpp:1417-1418
     const uint32_t uH = exact ? size[1] : (uint32_t)(cfg->upscale * (float)H);
-    if (exact) {
+    if (view) {
+        // fftup_plan_create_view: every rule of such a plan, here (arithmetic, before any device access); the blocks of the other
+        // plan kinds below do not apply
+        if (W < 2 || H < 2 || uW < 2 || uH < 2) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_view: every length (width, height, out_width, out_height) must be at least 2");
+        if (int rc = check_view("fftup_plan_create_view", view, uW, uH)) return rc;
+        if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "fftup_plan_create_view plans exist for -p 0 and -p 2");
+        if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view covers the FFT mode only (no FFTUP_FLAG_DCT)");
+        if (W > 8192u) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: rows of at most 8192 points (no non-R2C or four-step path)");
+        if (2 * (uint64_t)(W / 2) + uW > 8192u || fftup_viewtab::conv_length(W, uW) > 8192u)
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: the row convolution length (2,3,5,7-smooth, at least 2 (width/2) + out_width) must be at most 8192");
+        for (uint32_t n : {W, H}) {
+            if (!is_smooth(n) && !(cfg->flags & FFTUP_FLAG_ANY_SIZE))
+                return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: width and height must factor into 2,3,5,7; FFTUP_FLAG_ANY_SIZE accepts any length up to 4096");
+            if (!is_smooth(n) && n > BZ_MAX_N)
+                return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: " + std::to_string(n) + " has a prime factor above 7 and is longer than 4096");
+        }
+        if (2 * (uint64_t)(H / 2) + uH > 16384u || !view_col_tk(H, uH))
+            return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: the columns must fit the LDS (two buffers of the column convolution length at a tile width of 1)");
+        cfg_copy.upscale = view_factor(*view, uW, uH);
+    }
+    else if (exact) {
         // fftup_plan_create_size: each axis on its own, up, down or equal, either parity (arithmetic on the sizes)
         if (W < 2 || H < 2 || uW < 2 || uH < 2) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: every length (width, height, out_width, out_height) must be at least 2");
         if (align > FFTUP_ALIGN_CENTRE) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_create_size: align must be FFTUP_ALIGN_CORNER (0) or FFTUP_ALIGN_CENTRE (1)");
@@ -469,10 +521,11 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
         return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_DOWNSCALE: the output sizes must be at least 2 and below the input's");
     // FFTUP_FLAG_ANY_SIZE: lengths with a prime factor above 7 run as Bluestein transforms; `bz`: this plan has one.  A plan
     // whose four lengths are smooth is the same plan with or without the flag.
-    const bool bz = !is_smooth(W) || !is_smooth(H) || !is_smooth(uW) || !is_smooth(uH);
+    // (view plans: only the forward transforms have the input's lengths; the output lengths are the chirp-z transforms' business)
+    const bool bz = !is_smooth(W) || !is_smooth(H) || (!view && (!is_smooth(uW) || !is_smooth(uH)));
     if (bz && !(cfg->flags & FFTUP_FLAG_ANY_SIZE))
         return fail(FFTUP_E_UNSUPPORTED_SIZE, "sizes must factor into 2,3,5,7 (vkFFT.h:4719-4726); FFTUP_FLAG_ANY_SIZE accepts any even length up to 4096");
-    if (bz) {
+    if (bz && !view) {
         // (arithmetic on the sizes, before any device access)
         if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_DCT plans need sizes that factor into 2,3,5,7 (FFTUP_FLAG_ANY_SIZE covers the FFT modes only)");
         if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "FFTUP_FLAG_ANY_SIZE plans with a non-smooth length exist for -p 0 and -p 2");
@@ -494,7 +547,7 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
         if (!bluestein_col_tk(H, uH))
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ODD_SIZE: a plan with an odd length needs columns that fit the LDS (no four-step columns)");
     }
-    if (exact) {
+    if (exact && !view) {
         // the same bounds: these plans run the odd-size plans' kernels
         if (cfg->flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_size covers the FFT mode only (no FFTUP_FLAG_DCT)");
         if (cfg->precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "fftup_plan_create_size plans exist for -p 0 and -p 2");
@@ -550,10 +603,12 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
     P->odd = odd;
     P->exact = exact;
     P->align = exact ? align : 0;
+    P->view = view != nullptr;
     // (FFT downscale plans keep only the bins the output holds, kx <= uW/2: S1, S2 and the column pass shrink with the output)
     // (odd plans: the bins both lengths hold, kx <= min(W, uW)/2 -- floor: an odd length has (n + 1)/2 bins from 0 up, no Nyquist bin)
     P->ncols = cplx ? (int)W : (down && !dct) ? (int)(uW / 2 + 1) : (int)(W / 2 + 1);
     if (odd) P->ncols = (int)(std::min(W, uW) / 2 + 1);
+    if (view) P->ncols = (int)(W / 2 + 1);              // (the worst case: the buffers below hold any view; view_apply sets the current one)
     P->esz = P->dbl ? 8 : (P->half ? 2 : 4);
     P->csz = P->dbl ? 16 : 8;
     P->device = cfg->device;
@@ -627,6 +682,13 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
             }
             // a Bluestein column transform: buffers of L * TK points (bluestein_col_tk: checked before any device access); the
             // column kernel of an odd plan is sized the same way, max(length, L) * TK with L = length for a smooth one
+            if (view) {
+                P->vx.L = fftup_viewtab::conv_length(W, uW); P->vy.L = fftup_viewtab::conv_length(H, uH);
+                P->vx.planL = make_stage_plan(P->vx.L); P->vy.planL = make_stage_plan(P->vy.L);
+                P->TK = view_col_tk(H, uH);
+                P->ldsCol = 2 * P->csz * (size_t)lpad_size((int)(std::max(lds_length(H, P->TK), P->vy.L) * (uint32_t)P->TK));
+                if (P->ldsCol > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: this device's LDS does not hold the column transform"); goto bad; }
+            }
             if (!P->TK && (odd || !is_smooth(H) || !is_smooth(uH))) {
                 P->TK = bluestein_col_tk(H, uH);
                 P->ldsCol = 2 * P->csz * (size_t)lpad_size((int)(std::max(std::max(H, uH), std::max(lds_length(H, P->TK), lds_length(uH, P->TK))) * (uint32_t)P->TK));
@@ -707,6 +769,7 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
             if (!rows_fit(W)) { four(P->fourF, W); P->ldsRowF = 0; }
             if (!rows_fit(uW)) { four(P->fourI, uW); P->ldsRowI = 0; }
         }
+        if (view) P->ldsRowI = 2 * P->csz * (size_t)lpad_size((int)P->vx.L);      // (L_x >= out_width)
         if (P->ldsRowI > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "upscaled width too large for LDS"); goto bad; }
         {
             const int tmax = kernels_generic_max_threads(P->dbl);
@@ -717,6 +780,10 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
                 P->thrW = std::min(tmax, std::max(64, round_up((int)lds_length(W, 1) / 8, 64)));
                 P->thrUW = std::min(tmax, std::max(64, round_up((int)lds_length(uW, 1) / 8, 64)));
                 if (!P->poly) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(lds_length(H, P->TK), lds_length(uH, P->TK)) * P->TK / 8, 64)));
+            }
+            if (view) {                                      // the chirp-z transforms: one thread per eight points of L
+                P->thrUW = std::min(tmax, std::max(64, round_up((int)P->vx.L / 8, 64)));
+                P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(lds_length(H, P->TK), P->vy.L) * P->TK / 8, 64)));
             }
             // -p 1 R2C rows: one LDS buffer where every stage runs in place with 8 points per thread (two workgroups per compute unit)
             if (P->dbl && !cplx) {
@@ -738,7 +805,7 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
         if (bz) {
             const std::pair<BzPlan*, uint32_t> axes[4] = {{&P->bzW, W}, {&P->bzH, H}, {&P->bzUW, uW}, {&P->bzUH, uH}};
             for (int i = 0; i < 4; i++)
-                if (!is_smooth(axes[i].second)) {
+                if (!is_smooth(axes[i].second) && !(view && i >= 2)) {
                     const uint32_t L = lds_length(axes[i].second, (i & 1) ? P->TK : 1);
                     PLAN_RC(make_bluestein(P, axes[i].first, axes[i].second, L, make_stage_plan(L)));
                 }
@@ -746,6 +813,16 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
         if (exact && align == FFTUP_ALIGN_CENTRE) {
             PLAN_RC(make_phases(P, &P->phW, W, uW));
             PLAN_RC(make_phases(P, &P->phH, H, uH));
+        }
+        if (view) {
+            // tables of the worst case: 2 (N/2) + 1 bins in, M points out, L points of the convolution
+            const std::pair<fftup_plan::ViewAxis*, std::pair<uint32_t, uint32_t>> vaxes[2] = {{&P->vx, {W, uW}}, {&P->vy, {H, uH}}};
+            for (auto& va : vaxes) {
+                PLAN_RC(make_twiddles(P, &va.first->tw, va.first->L));
+                PLAN_RC(dev_alloc(P, (void**)&va.first->pre, sizeof(float2) * (2 * (size_t)(va.second.first / 2) + 1)));
+                PLAN_RC(dev_alloc(P, (void**)&va.first->post, sizeof(float2) * va.second.second));
+                PLAN_RC(dev_alloc(P, (void**)&va.first->bhat, sizeof(float2) * va.first->L));
+            }
         }
         if (dct) {
             PLAN_RC(make_rotations(P, &P->rotW, W));
@@ -798,6 +875,7 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
                 if (t4_bytes) PLAN_RC(dev_alloc(P, &P->lanes[l].T4, t4_bytes));
             }
         }
+        if (view) PLAN_RC(view_apply(P, *view, true));       // (after the allocations above: they are the worst case's)
         PLAN_RC(kernels_set_attributes(P));          // dynamic LDS above 64 KB for the kernels THIS plan launches (fftup_launch.hip)
         if (P->mixed == 3 && ((cfg->flags & FFTUP_FLAG_TUNE_PLAN) || jit_tune_enabled())) tune_fused(P);
     }
@@ -819,12 +897,38 @@ int fftup_plan_create_size(fftup_plan** out, const fftup_config* cfg, uint32_t o
     return plan_create(out, cfg, size, align);
 }
 
+int fftup_plan_create_view(fftup_plan** out, const fftup_config* cfg, uint32_t out_width, uint32_t out_height, const fftup_view* view)
+{
+    if (out) *out = nullptr;
+    if (!out || !cfg || !view) return fail(FFTUP_E_INVALID_ARG, "null argument");
+    const uint32_t size[2] = {out_width, out_height};
+    return plan_create(out, cfg, size, FFTUP_ALIGN_CORNER, view);
+}
+
+int fftup_plan_set_view(fftup_plan* P, const fftup_view* view)
+{
+    if (!P || !view) return fail(FFTUP_E_INVALID_ARG, "null argument");
+    if (!P->view) return fail(FFTUP_E_INVALID_ARG, "fftup_plan_set_view: not a view plan (fftup_plan_create_view makes one)");
+    if (int rc = check_view("fftup_plan_set_view", view, P->uW, P->uH)) return rc;
+    HIP_TRY(hipSetDevice(P->device));
+    // the tables are read by the kernels of frames in flight: wait for the plan's own streams first
+    for (auto& lane : P->lanes) HIP_TRY(hipStreamSynchronize(lane.stream));
+    return view_apply(P, *view, false);
+}
+
 int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
 {
     if (!P || !buf || !buflen) return fail(FFTUP_E_INVALID_ARG, "null argument");
     std::string s;
     if (P->down && P->dct) s = "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
                                + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
+    else if (P->view) {
+        char t[256];
+        snprintf(t, sizeof t, "view: chirp-z resampling, rows %u->%u origin %.17g span %.17g (kmax %d, L=%u), columns %u->%u origin %.17g span %.17g (kmax %d, L=%u)",
+                 P->W, P->uW, P->vw.origin_x, P->vw.span_x, P->vx.kmax, P->vx.L, P->H, P->uH, P->vw.origin_y, P->vw.span_y, P->vy.kmax, P->vy.L);
+        s = std::string(t) + " (size-generic kernels, " + std::to_string(P->ncols) + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of "
+            + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
+    }
     else if (P->exact) s = "exact size: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
                            + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH)
                            + (P->align == FFTUP_ALIGN_CENTRE ? ", pixel centres aligned" : ", pixel 0 on pixel 0") + " (size-generic kernels, " + std::to_string(P->ncols)
@@ -848,7 +952,11 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
         if (f.on) s += std::string("; ") + what + " in four steps " + std::to_string(f.n1) + "*" + std::to_string(f.n2) + " (tiles of " + std::to_string(f.tka) + " / " + std::to_string(f.tkb) + ")";
     };
     four("forward rows", P->fourF); four("inverse rows", P->fourI); four("forward columns", P->colF); four("inverse columns", P->colI);
-    if (P->bz) {
+    if (P->bz && P->view) {
+        if (P->bzW.L) s += "; forward rows bluestein L=" + std::to_string(P->bzW.L);
+        if (P->bzH.L) s += "; forward columns bluestein L=" + std::to_string(P->bzH.L);
+    }
+    else if (P->bz) {
         // the Bluestein axes and their lengths L (forward / inverse; "-": that transform is a direct one)
         auto axis = [&](const char* what, uint32_t n, uint32_t un, const BzPlan& f, const BzPlan& i) {
             if (!f.L && !i.L) return;
@@ -922,9 +1030,14 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     // rounded UP to pairs, the bytes are not: the tail workgroup moves one row.  Their names (kernels_odd.hpp):
     if (P->odd)
         for (int i = 0; i < 3; i++) strncat(info->kernel_names[i], "_odd", 63 - strlen(info->kernel_names[i]));
+    if (P->view) {                                           // (kernels_view.hpp; the row R2C kernel is the odd-size plans')
+        snprintf(info->kernel_names[0], 64, "row_r2c_odd");
+        snprintf(info->kernel_names[1], 64, "col_view");
+        snprintf(info->kernel_names[2], 64, "row_view_c2r");
+    }
     // kernels with a Bluestein transform (kernels_bluestein.hpp)
     const bool kbz[3] = {P->bzW.L != 0, P->bzH.L != 0 || P->bzUH.L != 0, P->bzUW.L != 0};
-    for (int i = 0; i < 3; i++)
+    for (int i = 0; i < (P->view ? 2 : 3); i++)
         if (kbz[i]) strncat(info->kernel_names[i], "_bz", 63 - strlen(info->kernel_names[i]));
     return FFTUP_OK;
 }

@@ -105,6 +105,14 @@ struct fftup_plan {
     bool exact = false;
     uint32_t align = 0;
     float2 *phW = nullptr, *phH = nullptr;
+    // fftup_plan_create_view: the frame's trigonometric interpolant at origin + m span / M per axis (kernels_view.hpp).  Buffers and
+    // the convolution lengths are sized for the worst case of W, H, uW, uH (kmax = N/2), so fftup_plan_set_view re-aims the plan in
+    // place; ncols = kmax_x + 1 and NT follow the CURRENT view.  Per axis: kmax, the smooth convolution length L with its roots,
+    // and the three chirp tables (view_tables.hpp)
+    bool view = false;
+    fftup_view vw{};
+    struct ViewAxis { int kmax = 0; uint32_t L = 0; StagePlan planL{}; float2 *tw = nullptr, *pre = nullptr, *post = nullptr, *bhat = nullptr; };
+    ViewAxis vx, vy;
     int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
     int pairs_per_strip = 6;
     bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
