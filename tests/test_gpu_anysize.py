@@ -106,8 +106,9 @@ def _check(W, H, u, precision, down, uint8, seed, tag):
 
 
 # 46x22: Bluestein on all four transforms; 640x482: columns only (482 = 2 * 241); 1000x800 -u 1.1: the inverses only (1100, 880);
-# 4094x64 -u 1: L = 8192
-UP = [(46, 22, 2.0), (640, 482, 2.0), (1000, 800, 1.1), (92, 44, 1.5), (1170, 844, 2.0), (4094, 64, 1.0)]
+# 4094x64 -u 1: L = 8192; 16x262: a thin frame whose Bluestein column pass (524 points through L = 1050, tiles of 8) needs 142 816 bytes
+# of dynamic LDS -- above the 64 KB a kernel gets without its attribute
+UP = [(46, 22, 2.0), (640, 482, 2.0), (1000, 800, 1.1), (92, 44, 1.5), (1170, 844, 2.0), (4094, 64, 1.0), (16, 262, 2.0)]
 
 
 @pytest.mark.parametrize("W,H,u", UP)

@@ -111,7 +111,10 @@ def _precisions(W, H, u):
 # 105x63 -u 1: the identity on smooth odd lengths; 90x45 -u 1.5 (135x67): the only odd length is H ... and uH; 64x45 -u 2: H only;
 # 50x32 -u 1.5 (75x48): uW only
 EXTRA = [(105, 63, 1.0, "", None), (64, 45, 2.0, "", None), (50, 32, 1.5, "", None)]
-CASES = [(W, H, u, extra, p, u8) for (W, H, u, extra, _) in VALID + VALID_ANY + EXTRA for p in _precisions(W, H, u) for u8 in (False, True)]
+# 15x243 -u 2: a thin frame whose column pass (486 points, tiles of 8) needs 66 112 bytes of dynamic LDS -- above the 64 KB a kernel
+# gets without its attribute
+THIN = [(15, 243, 2.0, "", None)]
+CASES = [(W, H, u, extra, p, u8) for (W, H, u, extra, _) in VALID + VALID_ANY + EXTRA + THIN for p in _precisions(W, H, u) for u8 in (False, True)]
 
 
 @pytest.mark.parametrize("W,H,u,extra,precision,uint8", CASES)

@@ -98,9 +98,14 @@ def test_full_frame_lattice_against_both_oracles(W, H, uW, uH, extra, align):
            "view full p0 %dx%d->%dx%d a%d %s" % (W, H, uW, uH, align, extra), y=lambda x: E.resample_planes(x, uW, uH, align))
 
 
+# the full frame of 16x256 at 32x512: a thin frame whose column pass (convolution length 768, tiles of 8) needs 104 464 bytes of
+# dynamic LDS -- above the 64 KB a kernel gets without its attribute
+THIN = [(16, 256, 32, 512, (0.0, 0.0), (16.0, 256.0), "")]
+
+
 @pytest.mark.parametrize("uint8", [False, True])
 @pytest.mark.parametrize("precision", [0, 2])
-@pytest.mark.parametrize("W,H,uW,uH,origin,span,extra", VIEWS)
+@pytest.mark.parametrize("W,H,uW,uH,origin,span,extra", VIEWS + THIN)
 def test_view_parity(W, H, uW, uH, origin, span, extra, precision, uint8):
     _check(W, H, uW, uH, origin, span, precision, extra, uint8, W + H + uW + precision,
            "view p%d %dx%d->%dx%d o%s s%s %s u8%d" % (precision, W, H, uW, uH, origin, span, extra, uint8))

@@ -96,6 +96,15 @@ int dev_alloc(fftup_plan* P, void** ptr, size_t bytes)
     return FFTUP_OK;
 }
 
+// a table of fp32 pairs computed on the host: device memory owned by the plan, blocking copy
+static int upload_table(fftup_plan* P, float2** dptr, const std::vector<float2>& h)
+{
+    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * h.size());
+    if (rc) return rc;
+    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * h.size(), hipMemcpyHostToDevice));
+    return FFTUP_OK;
+}
+
 static int make_twiddles(fftup_plan* P, float2** dptr, uint32_t n)
 {
     if (P->dbl) {                     // double2 table behind the same pointer member
@@ -115,10 +124,7 @@ static int make_twiddles(fftup_plan* P, float2** dptr, uint32_t n)
         double a = 2.0 * M_PI * (double)k / (double)n;
         h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
-    return FFTUP_OK;
+    return upload_table(P, dptr, h);
 }
 
 // DCT plans: the pre- and post-rotations exp(i pi k / 2n), k < n, in double, rounded once to fp32 (as make_twiddles)
@@ -129,10 +135,7 @@ static int make_rotations(fftup_plan* P, float2** dptr, uint32_t n)
         const double a = M_PI * (double)k / (2.0 * (double)n);
         h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
-    return FFTUP_OK;
+    return upload_table(P, dptr, h);
 }
 
 // ---- FFTUP_FLAG_ANY_SIZE: lengths with a prime factor above 7 run as Bluestein transforms (kernels_bluestein.hpp)
@@ -198,8 +201,21 @@ static float const_via_percent_f(double v, bool half)
     return f;
 }
 
-// the row kernel reads uint8 RGB directly (fp32 / fp16 plans only)
 static int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// threads of a workgroup whose LDS sequences hold `points` points in all: one per eight points, whole waves, at most `tmax`
+static int fft_threads(int points, int tmax) { return std::min(tmax, std::max(64, round_up(points / 8, 64))); }
+// The four-step plan of a transform of n points (split_four): the factors' radix lists, LDS bytes and threads of both passes.
+// false: no split fits the LDS
+static bool make_four(const fftup_plan* P, fftup_plan::Four& f, uint32_t n)
+{
+    f.on = split_four(n, P->csz, &f.n1, &f.n2, &f.tka, &f.tkb);
+    if (!f.on) return false;
+    f.p1 = make_stage_plan((uint32_t)f.n1); f.p2 = make_stage_plan((uint32_t)f.n2);
+    f.ldsA = 2 * P->csz * (size_t)lpad_size(f.n1 * f.tka); f.ldsB = 2 * P->csz * (size_t)lpad_size(f.n2 * f.tkb);
+    const int tmax = kernels_generic_max_threads(P->dbl);
+    f.thrA = fft_threads(f.n1 * f.tka, tmax); f.thrB = fft_threads(f.n2 * f.tkb, tmax);
+    return true;
+}
 
 static bool jit_enabled()
 {
@@ -400,10 +416,7 @@ static int make_phases(fftup_plan* P, float2** dptr, uint32_t N, uint32_t M)
         const double a = -M_PI * (double)r / ((double)M * (double)N);
         h[k] = make_float2((float)std::cos(a), (float)std::sin(a));
     }
-    int rc = dev_alloc(P, (void**)dptr, sizeof(float2) * n);
-    if (rc) return rc;
-    HIP_TRY(hipMemcpy(*dptr, h.data(), sizeof(float2) * n, hipMemcpyHostToDevice));
-    return FFTUP_OK;
+    return upload_table(P, dptr, h);
 }
 
 // ---- fftup_plan_create_view (kernels_view.hpp, view_tables.hpp)
@@ -706,15 +719,8 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
         if (!P->TK) {
             // not even one column fits: tiles of one column, both column transforms in four steps through HBM (k_row4_a / k_row4_b)
             P->TK = 1; P->ldsCol = 0;
-            for (auto fh : {std::make_pair(&P->colF, H), std::make_pair(&P->colI, uH)}) {
-                fftup_plan::Four& f = *fh.first;
-                f.on = split_four(fh.second, P->csz, &f.n1, &f.n2, &f.tka, &f.tkb);
-                if (!f.on) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "column too long: no four-step split of the height fits the LDS"); goto bad; }
-                f.p1 = make_stage_plan((uint32_t)f.n1); f.p2 = make_stage_plan((uint32_t)f.n2);
-                f.ldsA = 2 * P->csz * (size_t)lpad_size(f.n1 * f.tka); f.ldsB = 2 * P->csz * (size_t)lpad_size(f.n2 * f.tkb);
-                const int tmax = kernels_generic_max_threads(P->dbl);
-                f.thrA = std::min(tmax, std::max(64, round_up(f.n1 * f.tka / 8, 64)));
-                f.thrB = std::min(tmax, std::max(64, round_up(f.n2 * f.tkb / 8, 64)));
+            if (!make_four(P, P->colF, H) || !make_four(P, P->colI, uH)) {
+                rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "column too long: no four-step split of the height fits the LDS"); goto bad;
             }
         }
         if (aot && !P->dbl && !cplx && !dct && !down && !exact && !P->tuned && !(cfg->flags & FFTUP_FLAG_GENERIC_KERNELS) && uW == 2 * W && uH == 2 * H && P->TK >= 4) {
@@ -743,6 +749,18 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
             }
         }
         if (P->tuned || P->mixed) P->poly = false;               // (their own column kernels)
+        // The family, decided here once.  The rules above make the families exclusive wherever two of them could claim a plan (the
+        // long rows of cplx and the double arithmetic of f64 exist in the size-generic upscale kernels only; the ahead-of-time and
+        // plan-time kernels take none of the other modes): stated here, so that no order of tests has to be relied on.  Three
+        // pairs are no conflict: view plans are `odd` and `exact` (they run the odd plans' row kernel), odd plans may be `down`
+        // (the direction is a parameter of their kernels), DCT plans may be `down` too.
+        if ((cplx && (dct || down || odd || view || bz)) || (P->dbl && (dct || down || odd || view || bz)) || (dct && (odd || view || bz)) ||
+            ((P->tuned || P->mixed) && (cplx || P->dbl || dct || down || odd || view || bz)) || (P->tuned && P->mixed)) {
+            rc = fail(FFTUP_E_INVALID_ARG, "internal: the plan rules let two kernel families claim this plan"); goto bad;
+        }
+        using Family = fftup_plan::Family;
+        P->family = cplx ? Family::cplx : P->dbl ? Family::f64 : dct ? Family::dct : view ? Family::view : odd ? Family::odd : down ? Family::down
+                    : P->tuned ? Family::tuned : P->mixed == 3 ? Family::mixed_jit : P->mixed ? Family::mixed_aot : Family::generic;
         P->fused = (P->tuned || P->mixed) && !(cfg->flags & FFTUP_FLAG_UNFUSED_SHARPEN);
         P->u8out = P->fused && (cfg->flags & FFTUP_FLAG_FUSE_U8_STORE);
         set_strip_length(P);
@@ -758,32 +776,25 @@ static int plan_create(fftup_plan** out, const fftup_config* cfg_in, const uint3
             P->inplaceF = rows_fit(W) == 1; P->inplaceI = rows_fit(uW) == 1;
             if (P->inplaceF) P->ldsRowF /= 2;
             if (P->inplaceI) P->ldsRowI /= 2;
-            auto four = [&](fftup_plan::Four& f, uint32_t n) {           // ... or four steps through HBM
-                f.on = split_four(n, P->csz, &f.n1, &f.n2, &f.tka, &f.tkb);
-                f.p1 = make_stage_plan((uint32_t)f.n1); f.p2 = make_stage_plan((uint32_t)f.n2);
-                f.ldsA = 2 * P->csz * (size_t)lpad_size(f.n1 * f.tka); f.ldsB = 2 * P->csz * (size_t)lpad_size(f.n2 * f.tkb);
-                const int tmax = kernels_generic_max_threads(P->dbl);
-                f.thrA = std::min(tmax, std::max(64, round_up(f.n1 * f.tka / 8, 64)));
-                f.thrB = std::min(tmax, std::max(64, round_up(f.n2 * f.tkb / 8, 64)));
-            };
-            if (!rows_fit(W)) { four(P->fourF, W); P->ldsRowF = 0; }
-            if (!rows_fit(uW)) { four(P->fourI, uW); P->ldsRowI = 0; }
+            // ... or four steps through HBM (a split exists: checked before any device access)
+            if (!rows_fit(W)) { make_four(P, P->fourF, W); P->ldsRowF = 0; }
+            if (!rows_fit(uW)) { make_four(P, P->fourI, uW); P->ldsRowI = 0; }
         }
         if (view) P->ldsRowI = 2 * P->csz * (size_t)lpad_size((int)P->vx.L);      // (L_x >= out_width)
         if (P->ldsRowI > lds_max) { rc = fail(FFTUP_E_UNSUPPORTED_SIZE, "upscaled width too large for LDS"); goto bad; }
         {
             const int tmax = kernels_generic_max_threads(P->dbl);
-            P->thrW = std::min(tmax, std::max(64, round_up((int)W / 8, 64)));
-            P->thrUW = std::min(tmax, std::max(64, round_up((int)uW / 8, 64)));
-            if (!(P->poly || P->inplaceC)) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(H, uH) * P->TK / 8, 64)));     // (in-place column plans chose theirs above)
-            if (bz) {                                        // one thread per eight points of the sequences in LDS, as above
-                P->thrW = std::min(tmax, std::max(64, round_up((int)lds_length(W, 1) / 8, 64)));
-                P->thrUW = std::min(tmax, std::max(64, round_up((int)lds_length(uW, 1) / 8, 64)));
-                if (!P->poly) P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(lds_length(H, P->TK), lds_length(uH, P->TK)) * P->TK / 8, 64)));
+            P->thrW = fft_threads((int)W, tmax);
+            P->thrUW = fft_threads((int)uW, tmax);
+            if (!(P->poly || P->inplaceC)) P->thrCol = fft_threads((int)std::max(H, uH) * P->TK, tmax);     // (in-place column plans chose theirs above)
+            if (bz) {                                        // the sequences in LDS are the Bluestein transforms'
+                P->thrW = fft_threads((int)lds_length(W, 1), tmax);
+                P->thrUW = fft_threads((int)lds_length(uW, 1), tmax);
+                if (!P->poly) P->thrCol = fft_threads((int)std::max(lds_length(H, P->TK), lds_length(uH, P->TK)) * P->TK, tmax);
             }
-            if (view) {                                      // the chirp-z transforms: one thread per eight points of L
-                P->thrUW = std::min(tmax, std::max(64, round_up((int)P->vx.L / 8, 64)));
-                P->thrCol = std::min(tmax, std::max(64, round_up((int)std::max(lds_length(H, P->TK), P->vy.L) * P->TK / 8, 64)));
+            if (view) {                                      // the chirp-z transforms: the sequences hold L points
+                P->thrUW = fft_threads((int)P->vx.L, tmax);
+                P->thrCol = fft_threads((int)std::max(lds_length(H, P->TK), P->vy.L) * P->TK, tmax);
             }
             // -p 1 R2C rows: one LDS buffer where every stage runs in place with 8 points per thread (two workgroups per compute unit)
             if (P->dbl && !cplx) {
@@ -920,39 +931,51 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
 {
     if (!P || !buf || !buflen) return fail(FFTUP_E_INVALID_ARG, "null argument");
     std::string s;
-    if (P->down && P->dct) s = "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
-                               + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
-    else if (P->view) {
+    using Family = fftup_plan::Family;
+    const std::string half = P->half ? ", half storage" : "", tiles = std::to_string(P->TK);
+    // (odd, exact and view plans)
+    const std::string resampled = " (size-generic kernels, " + std::to_string(P->ncols) + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + tiles + ")" + half;
+    const std::string rows_cols = ", rows " + std::to_string(P->W) + "->" + std::to_string(P->uW) + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH);
+    switch (P->family) {
+    case Family::dct:
+        s = std::string(P->down ? "downscale: dct: size-generic DCT-II / truncate / DCT-III kernels" : "dct: size-generic DCT-II / zero-pad / DCT-III kernels")
+            + " (LDS ping-pong, run-time radix lists, column tiles of " + tiles + " column pairs)" + half;
+        break;
+    case Family::view: {
         char t[256];
         snprintf(t, sizeof t, "view: chirp-z resampling, rows %u->%u origin %.17g span %.17g (kmax %d, L=%u), columns %u->%u origin %.17g span %.17g (kmax %d, L=%u)",
                  P->W, P->uW, P->vw.origin_x, P->vw.span_x, P->vx.kmax, P->vx.L, P->H, P->uH, P->vw.origin_y, P->vw.span_y, P->vy.kmax, P->vy.L);
-        s = std::string(t) + " (size-generic kernels, " + std::to_string(P->ncols) + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of "
-            + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
+        s = t + resampled;
+        break;
     }
-    else if (P->exact) s = "exact size: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
-                           + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH)
-                           + (P->align == FFTUP_ALIGN_CENTRE ? ", pixel centres aligned" : ", pixel 0 on pixel 0") + " (size-generic kernels, " + std::to_string(P->ncols)
-                           + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
-    else if (P->odd) s = std::string(P->down ? "downscale: " : "") + "odd sizes: exact trigonometric resampling, rows " + std::to_string(P->W) + "->" + std::to_string(P->uW)
-                         + ", columns " + std::to_string(P->H) + "->" + std::to_string(P->uH) + " (size-generic kernels, " + std::to_string(P->ncols)
-                         + " spectrum columns, LDS ping-pong, run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
-    else if (P->down) s = "downscale: size-generic kernels, spectrum cropped to " + std::to_string(P->ncols) + " columns at the row stage (LDS ping-pong, "
-                          "run-time radix lists, column tiles of " + std::to_string(P->TK) + ")" + (P->half ? ", half storage" : "");
-    else if (P->dct) s = "dct: size-generic DCT-II / zero-pad / DCT-III kernels (LDS ping-pong, run-time radix lists, column tiles of "
-                    + std::to_string(P->TK) + " column pairs)" + (P->half ? ", half storage" : "");
-    else if (P->mixed == 3) s = "specialised at plan time: " + fftup_jit::describe(P->jit->choice);
-    else if (P->tuned) s = "ahead-of-time power-of-two kernels (radix 8, 8 points per thread; fused C2R+sharpen " + std::string(P->fused ? "on" : "off") + ")"
-                           + "; column kernel with digit-swap exchanges";
-    else if (P->mixed) s = std::string("ahead-of-time mixed-radix kernels: ") + (P->mixed == 1 ? "row 15*8*16, col 9*10*12, fused 16*16*15" : "row 5*16*16, col 9*8*10, fused 16*16*10");
-    else if (P->cplx) s = "size-generic kernels, non-R2C path (full complex transforms)";
-    else s = std::string("size-generic kernels (") + ((P->inplaceF || P->inplaceI || P->inplaceC) ? "in place in one LDS buffer" : "LDS ping-pong") + ", run-time radix lists"
-             + (P->poly ? ", polyphase column pass)" : ")")
-             + (P->dbl ? ", double" : "");
+    case Family::odd:
+        if (P->exact) s = "exact size: exact trigonometric resampling" + rows_cols + (P->align == FFTUP_ALIGN_CENTRE ? ", pixel centres aligned" : ", pixel 0 on pixel 0") + resampled;
+        else s = std::string(P->down ? "downscale: " : "") + "odd sizes: exact trigonometric resampling" + rows_cols + resampled;
+        break;
+    case Family::down:
+        s = "downscale: size-generic kernels, spectrum cropped to " + std::to_string(P->ncols) + " columns at the row stage (LDS ping-pong, "
+            "run-time radix lists, column tiles of " + tiles + ")" + half;
+        break;
+    case Family::mixed_jit: s = "specialised at plan time: " + fftup_jit::describe(P->jit->choice); break;
+    case Family::tuned:
+        s = "ahead-of-time power-of-two kernels (radix 8, 8 points per thread; fused C2R+sharpen " + std::string(P->fused ? "on" : "off") + ")"
+            + "; column kernel with digit-swap exchanges";
+        break;
+    case Family::mixed_aot:
+        s = std::string("ahead-of-time mixed-radix kernels: ") + (P->mixed == 1 ? "row 15*8*16, col 9*10*12, fused 16*16*15" : "row 5*16*16, col 9*8*10, fused 16*16*10");
+        break;
+    case Family::cplx: s = "size-generic kernels, non-R2C path (full complex transforms)"; break;
+    case Family::generic: case Family::f64:
+        s = std::string("size-generic kernels (") + ((P->inplaceF || P->inplaceI || P->inplaceC) ? "in place in one LDS buffer" : "LDS ping-pong") + ", run-time radix lists"
+            + (P->poly ? ", polyphase column pass)" : ")")
+            + (P->dbl ? ", double" : "");
+        break;
+    }
     auto four = [&](const char* what, const fftup_plan::Four& f) {
         if (f.on) s += std::string("; ") + what + " in four steps " + std::to_string(f.n1) + "*" + std::to_string(f.n2) + " (tiles of " + std::to_string(f.tka) + " / " + std::to_string(f.tkb) + ")";
     };
     four("forward rows", P->fourF); four("inverse rows", P->fourI); four("forward columns", P->colF); four("inverse columns", P->colI);
-    if (P->bz && P->view) {
+    if (P->bz && P->family == Family::view) {
         if (P->bzW.L) s += "; forward rows bluestein L=" + std::to_string(P->bzW.L);
         if (P->bzH.L) s += "; forward columns bluestein L=" + std::to_string(P->bzH.L);
     }
@@ -1021,23 +1044,24 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     snprintf(info->device_name, sizeof info->device_name, "%s", device_label(P->prop));
     // (fftup_plan_create_size: the direction is a property of the axis, the row kernel crops when uW < W, the column kernel when uH < H)
     const bool crop_rows = P->exact ? P->uW < P->W : P->down, crop_cols = P->exact ? P->uH < P->H : P->down;
-    snprintf(info->kernel_names[0], 64, P->dct ? "dct_row" : crop_rows ? "row_r2c_crop" : P->cplx ? "row_c2c" : "row_r2c");
-    snprintf(info->kernel_names[1], 64, P->dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : crop_cols ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
-    snprintf(info->kernel_names[2], 64, P->dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (P->cplx ? "row_c2c_inv" : "row_c2r"));
+    const bool is_dct = P->family == fftup_plan::Family::dct, is_cplx = P->family == fftup_plan::Family::cplx;
+    snprintf(info->kernel_names[0], 64, is_dct ? "dct_row" : crop_rows ? "row_r2c_crop" : is_cplx ? "row_c2c" : "row_r2c");
+    snprintf(info->kernel_names[1], 64, is_dct ? (P->down ? "dct_col_crop_idct" : "dct_col_pad_idct") : crop_cols ? "col_fwd_crop_inv" : "col_fwd_pad_inv");
+    snprintf(info->kernel_names[2], 64, is_dct ? "idct_row" : P->fused ? "row_c2r_sharpen" : (is_cplx ? "row_c2c_inv" : "row_c2r"));
     snprintf(info->kernel_names[3], 64, P->fused ? "-" : "sharpen");
     // S1 / S2 above hold P->ncols columns: W/2 + 1 with W/2 rounded DOWN (an odd W has (W + 1)/2 bins, none self-paired); odd plans
     // keep min(W, uW)/2 + 1.  The row kernels of an odd plan run (H + 1)/2 and (uH + 1)/2 workgroups per plane -- the rows are
     // rounded UP to pairs, the bytes are not: the tail workgroup moves one row.  Their names (kernels_odd.hpp):
-    if (P->odd)
+    if (P->family == fftup_plan::Family::odd)
         for (int i = 0; i < 3; i++) strncat(info->kernel_names[i], "_odd", 63 - strlen(info->kernel_names[i]));
-    if (P->view) {                                           // (kernels_view.hpp; the row R2C kernel is the odd-size plans')
+    if (P->family == fftup_plan::Family::view) {             // (kernels_view.hpp; the row R2C kernel is the odd-size plans')
         snprintf(info->kernel_names[0], 64, "row_r2c_odd");
         snprintf(info->kernel_names[1], 64, "col_view");
         snprintf(info->kernel_names[2], 64, "row_view_c2r");
     }
     // kernels with a Bluestein transform (kernels_bluestein.hpp)
     const bool kbz[3] = {P->bzW.L != 0, P->bzH.L != 0 || P->bzUH.L != 0, P->bzUW.L != 0};
-    for (int i = 0; i < (P->view ? 2 : 3); i++)
+    for (int i = 0; i < (P->family == fftup_plan::Family::view ? 2 : 3); i++)
         if (kbz[i]) strncat(info->kernel_names[i], "_bz", 63 - strlen(info->kernel_names[i]));
     return FFTUP_OK;
 }

@@ -1,7 +1,8 @@
 // plan.hpp -- what the translation units of libfftup.so share: the plan object behind the opaque fftup_plan of include/fftup.h,
 // error reporting, and the internal entry points between the units
 //   fftup_plan.hip     plan construction (launchResample's plan semantics, VkResample.cpp:1409-1617), info, the plan-time tuner
-//   fftup_launch.hip   the frame's kernel launches -- the only unit that instantiates the frame kernels
+//   fftup_launch.hip   the frame's kernel launches -- the only unit that instantiates the frame kernels: one selector per pass and
+//                      plan family (fftup_plan::Family) names the kernel, for the launch and for its LDS attribute alike
 //   fftup_execute.hip  upload / execute / download (performVulkanUpscale, VkResample.cpp:1249-1279, and the transfers)
 //   fftup_queue.hip    host-streamed frames: fftup_submit_rgb8 / fftup_wait / fftup_drain
 //   fftup_png.hip      the device-side PNG encoder's host side
@@ -75,6 +76,13 @@ struct fftup_plan {
     int thrW = 0, thrCol = 0, thrUW = 0;
     size_t ldsRowF = 0, ldsCol = 0, ldsRowI = 0;
     float upsq = 0, coef = 0;
+    // Which set of kernels runs the frame: decided ONCE, by plan_create, from the fields below (which stay: they also describe
+    // properties that cut across the families -- half, bz, exact, poly, fused, u8out, inplace*, down together with dct).  What
+    // launches, attributes and descriptions branch on.  generic: size-generic R2C kernels on fp32 / fp16 data; tuned: ahead-of-time
+    // power-of-two kernels; mixed_aot / mixed_jit: mixed-radix kernels compiled ahead of time / at plan time (`mixed` 1, 2 / 3);
+    // cplx: non-R2C path (either precision); f64: -p 1 R2C; dct (up or down); down: FFT downscale; odd: odd and exact sizes; view
+    enum class Family { generic, tuned, mixed_aot, mixed_jit, cplx, f64, dct, down, odd, view };
+    Family family = Family::generic;
     bool tuned = false;
     bool fused = false;               // sharpen fused into the C2R kernel (tuned plans)
     bool u8out = false;               // FFTUP_FLAG_FUSE_U8_STORE in effect: the fused kernel stores 8-bit RGB, `out` slots hold [uH][uW][3] bytes
@@ -182,12 +190,12 @@ inline int check_slot(fftup_plan* P, uint32_t slot)
     return FFTUP_OK;
 }
 
-// ---- fftup_launch.hip: everything that names a kernel
+// ---- fftup_launch.hip: everything that names a kernel (each instantiation once, in the selector of its pass and family)
 // facts about the kernels the planner needs (defined next to the kernels)
 int kernels_generic_max_threads(bool dbl);                        // threads per workgroup of the size-generic kernels
 int kernels_aot_mixed_plan(uint32_t W, uint32_t H);               // 1: 1920x1080, 2: 1280x720 (ahead-of-time mixed-radix plans), 0: none
 size_t kernels_tuned_col_lds(uint32_t H);                         // LDS bytes of the power-of-two column kernel
-int kernels_set_attributes(fftup_plan* P);                        // dynamic LDS sizes above 64 KB, for the kernels THIS plan launches
+int kernels_set_attributes(fftup_plan* P);                        // dynamic LDS sizes above 64 KB, for the kernels launch_frame's selectors give THIS plan
 // one frame on lane P->cur: `which` < 0 launches all of its kernels, 0..3 only that one, 22 = the pre-sharpen tap of a fused plan
 int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which);
 void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st);                  // the host loop of VR:1636-1685 as a kernel
