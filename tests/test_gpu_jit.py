@@ -83,7 +83,7 @@ U_CASES = [
     (1024, 576, 1.875),  # 15/8: -> 1920 x 1080, first radix 15, NI = 4 of 15
     (2048, 1024, 1.125), # -> 2304 x 1152
     # ratios with denominator 3, 5, 7 (round 5, DD = 3, 5, 7): whatever float the caller passes, where the reference's float arithmetic
-    # gives exact output sizes and the symmetric guard for THIS size (fftup_plan.hip: jit_factor)
+    # gives exact output sizes and the symmetric guard for THIS size (plan_rules.cpp: jit_factor)
     (1920, 1080, float(np.float32(4.0 / 3.0))),   # 1080p -> 1440p: fused 16*16*10, NI = 6 of 16 first-stage inputs non-zero
     (960, 540, float(np.float32(4.0 / 3.0))),     # -> 720p
     (1600, 900, 1.6),                             # 8/5: 900p -> 1440p

@@ -10,7 +10,7 @@ Both run the same three kernels per frame on the plan's FFTUP_STREAMS lanes.  Th
 warm-up), the median is the figure.  Both sides are timed on the host clock from the call to the end of the batch (execute_ring
 returns there; the device batch is asynchronous, so it is followed by an empty blocking fftup_device_copy, which only waits); the
 ring's own event time is kept beside it.  The ring = 1 plan is created with FFTUP_FLAG_OVERLAP_ITERATIONS, which lays the fused
-kernel's strips out for overlapping frames as a ring does (set_strip_length); `device_sequential_layout` is the same call on a plan
+kernel's strips out for overlapping frames as a ring does (strip_length, csrc/plan_rules.cpp); `device_sequential_layout` is the same call on a plan
 without the flag.  A record, not a gate: `device_minus_ring_us_per_frame` against `ring_spread_us_per_frame` (max - min of the seven
 ring batches) says whether the difference is above the noise.
 

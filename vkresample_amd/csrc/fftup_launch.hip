@@ -573,10 +573,10 @@ template <typename C> static void launch_columns(fftup_plan* P, hipStream_t st)
     Row4Params<C> q{};
     const fftup_plan::Four &f = P->colF, &g = P->colI;
     q.spec = (const C*)P->lanes[P->cur].S1; q.T = (C*)P->lanes[P->cur].T4; q.R = P->lanes[P->cur].S1;
-    q.tw1 = (const C*)f.tw1; q.tw2 = (const C*)f.tw2; q.twN = (const C*)P->twH; q.plan1 = f.p1; q.plan2 = f.p2;
+    q.tw1 = (const C*)P->colFtw.tw1; q.tw2 = (const C*)P->colFtw.tw2; q.twN = (const C*)P->twH; q.plan1 = f.p1; q.plan2 = f.p2;
     q.N = (int)P->H; q.N1 = f.n1; q.N2 = f.n2; q.rows = P->ncols; q.W = (int)P->H; q.TK = 1; q.NT = P->ncols; q.inv_norm = (S)1;
     launch_four(four_col_kernels<C>(P, false), f, q, P->ncols, st);
-    q.R = P->lanes[P->cur].S2; q.tw1 = (const C*)g.tw1; q.tw2 = (const C*)g.tw2; q.twN = (const C*)P->twUH; q.plan1 = g.p1; q.plan2 = g.p2;
+    q.R = P->lanes[P->cur].S2; q.tw1 = (const C*)P->colItw.tw1; q.tw2 = (const C*)P->colItw.tw2; q.twN = (const C*)P->twUH; q.plan1 = g.p1; q.plan2 = g.p2;
     q.N = (int)P->uH; q.N1 = g.n1; q.N2 = g.n2; q.zlx = P->zly; q.zrx = P->zry; q.inv_norm = (S)(1.0 / (double)P->uH);
     launch_four(four_col_kernels<C>(P, true), g, q, P->ncols, st);
 }
@@ -625,7 +625,7 @@ template <typename C> static int launch_frame_cplx(fftup_plan* P, uint32_t in_sl
     if ((which < 0 || which == 0) && P->fourF.on) {
         Row4Params<C> q{};
         const fftup_plan::Four& f = P->fourF;
-        q.T = (C*)P->lanes[P->cur].T4; q.S1 = (C*)P->lanes[P->cur].S1; q.tw1 = (const C*)f.tw1; q.tw2 = (const C*)f.tw2; q.twN = (const C*)P->twW;
+        q.T = (C*)P->lanes[P->cur].T4; q.S1 = (C*)P->lanes[P->cur].S1; q.tw1 = (const C*)P->fourFtw.tw1; q.tw2 = (const C*)P->fourFtw.tw2; q.twN = (const C*)P->twW;
         q.plan1 = f.p1; q.plan2 = f.p2; q.N = (int)P->W; q.N1 = f.n1; q.N2 = f.n2; q.rows = (int)P->H; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT;
         set_in(P, in_slot, kind, q);
         launch_four(four_fwd_kernels<C>(P, kind), f, q, (int)P->H, st);
@@ -642,7 +642,7 @@ template <typename C> static int launch_frame_cplx(fftup_plan* P, uint32_t in_sl
             Row4Params<C> q{};
             const fftup_plan::Four& f = P->fourI;
             q.spec = (const C*)P->lanes[P->cur].S2; q.T = (C*)P->lanes[P->cur].T4; q.R = P->lanes[P->cur].R;
-            q.tw1 = (const C*)f.tw1; q.tw2 = (const C*)f.tw2; q.twN = (const C*)P->twUW; q.plan1 = f.p1; q.plan2 = f.p2;
+            q.tw1 = (const C*)P->fourItw.tw1; q.tw2 = (const C*)P->fourItw.tw2; q.twN = (const C*)P->twUW; q.plan1 = f.p1; q.plan2 = f.p2;
             q.N = (int)P->uW; q.N1 = f.n1; q.N2 = f.n2; q.rows = (int)P->uH; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT; q.zlx = P->zlx; q.zrx = P->zrx;
             q.inv_norm = (S)(1.0 / (double)P->uW);
             launch_four(four_inv_kernels<C>(P), f, q, (int)P->uH, st);

@@ -1,6 +1,8 @@
 // plan.hpp -- what the translation units of libfftup.so share: the plan object behind the opaque fftup_plan of include/fftup.h,
 // error reporting, and the internal entry points between the units
-//   fftup_plan.hip     plan construction (launchResample's plan semantics, VkResample.cpp:1409-1617), info, the plan-time tuner
+//   plan_rules.cpp     the planner without a device: request checks and every decision of a plan (PlanGeometry, plan_rules.hpp)
+//   fftup_plan.hip     plan creation on the device (tables, buffers, streams), destruction, fftup_plan_set_view, the plan-time tuner
+//   fftup_info.hip     fftup_plan_describe / fftup_plan_info, error text, device enumeration
 //   fftup_launch.hip   the frame's kernel launches -- the only unit that instantiates the frame kernels: one selector per pass and
 //                      plan family (fftup_plan::Family) names the kernel, for the launch and for its LDS attribute alike
 //   fftup_execute.hip  upload / execute / download (performVulkanUpscale, VkResample.cpp:1249-1279, and the transfers)
@@ -23,16 +25,13 @@
 #include "bluestein_plan.hpp"
 #include "fft_engine.hpp"
 #include "jit.hpp"
+#include "plan_rules.hpp"
 #include "png_params.hpp"
 
-using fftup::StagePlan;
 using fftup::BzPlan;
 using fftup::PngParams;
 
-static constexpr int TUNED_TK = 4;     // column tile width of the size-specialised kernels
-
-// ---- errors: code + thread-local detail (fftup_last_error)
-int fail(int code, const std::string& msg);
+// ---- errors: fail() (plan_rules.hpp) + the HIP runtime's
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t _e = (expr);                                                                    \
@@ -57,72 +56,21 @@ struct EventList {
     hipEvent_t& operator[](size_t i) { return ev[i]; }
 };
 
-struct fftup_plan {
-    fftup_config cfg{};
-    uint32_t W = 0, H = 0, uW = 0, uH = 0;
-    uint32_t ring = 1;
-    bool half = false;                // -p 2: binary16 storage
-    bool dbl = false;                 // -p 1: double storage and arithmetic (size-generic kernels, double2 spectra)
-    size_t esz = 4, csz = 8;          // bytes per real / complex element in HBM
+struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what lives on the device
     int device = 0;
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipDeviceProp_t prop{};
-
-    // geometry
-    int TK = 8, NT = 0;
-    int zlx = 0, zrx = 0, zly = 0, zry = 0;
-    StagePlan planW{}, planH{}, planUW{}, planUH{};
-    int thrW = 0, thrCol = 0, thrUW = 0;
-    size_t ldsRowF = 0, ldsCol = 0, ldsRowI = 0;
-    float upsq = 0, coef = 0;
-    // Which set of kernels runs the frame: decided ONCE, by plan_create, from the fields below (which stay: they also describe
-    // properties that cut across the families -- half, bz, exact, poly, fused, u8out, inplace*, down together with dct).  What
-    // launches, attributes and descriptions branch on.  generic: size-generic R2C kernels on fp32 / fp16 data; tuned: ahead-of-time
-    // power-of-two kernels; mixed_aot / mixed_jit: mixed-radix kernels compiled ahead of time / at plan time (`mixed` 1, 2 / 3);
-    // cplx: non-R2C path (either precision); f64: -p 1 R2C; dct (up or down); down: FFT downscale; odd: odd and exact sizes; view
-    enum class Family { generic, tuned, mixed_aot, mixed_jit, cplx, f64, dct, down, odd, view };
-    Family family = Family::generic;
-    bool tuned = false;
-    bool fused = false;               // sharpen fused into the C2R kernel (tuned plans)
-    bool u8out = false;               // FFTUP_FLAG_FUSE_U8_STORE in effect: the fused kernel stores 8-bit RGB, `out` slots hold [uH][uW][3] bytes
-    int mixed = 0;                    // compile-time mixed-radix plans: 1 = 1920x1080 -> 3840x2160, 2 = 1280x720 -> 2560x1440,
-                                      // 3 = specialised at plan time for this size (jit.hpp), kernels in `jit`
-    fftup_jit::Module* jit = nullptr;
-    int U = 2;                        // integer upscale factor of a polyphase plan (tuned / mixed): S1 + U-1 residue buffers
-    bool cplx = false;                // non-R2C path (VR:1424 false): full complex transforms, uW beyond the R2C limit
-    bool dct = false;                 // FFTUP_FLAG_DCT: DCT-II -> zero-pad -> DCT-III (kernels_dct.hpp); S1 / S2 hold real [3][H][W] / [3][uH][W]
-    bool down = false;                // FFTUP_FLAG_DOWNSCALE: uW < W, uH < H; without dct the spectrum is cropped (kernels_downscale.hpp): ncols = uW/2 + 1
-    bool poly = false;                         // size-generic u = 2 plan: polyphase column kernel (k_col_poly), the C2R kernel reads the even rows from S1
-    bool inplaceC = false;                     // -p 1 R2C plans: the column kernel's two transforms in one LDS buffer (k_col<TK, double2, true>)
-    bool inplaceF = false, inplaceI = false;   // ... whose forward / inverse rows are too long for two LDS buffers: fft_lds_inplace
-    // ... and rows too long for ONE buffer: four steps through HBM (k_row4_a / k_row4_b), row length = n1 * n2
-    struct Four { bool on = false; int n1 = 0, n2 = 0, tka = 1, tkb = 1;    // N = n1 * n2; sequences per workgroup of pass A / pass B
-                  StagePlan p1{}, p2{}; float2 *tw1 = nullptr, *tw2 = nullptr; size_t ldsA = 0, ldsB = 0; int thrA = 64, thrB = 64; };
-    Four fourF, fourI;
-    Four colF, colI;                  // columns longer than the LDS (TK = 1): the same two kernels on dense columns
-    // FFTUP_FLAG_ANY_SIZE: per transform, L != 0 = the length has a prime factor above 7 and runs as a Bluestein transform of
-    // length L (kernels_bluestein.hpp); `bz`: the plan has at least one such transform (size-generic R2C kernels, fp32 arithmetic)
-    BzPlan bzW{}, bzH{}, bzUW{}, bzUH{};
-    bool bz = false;
-    // FFTUP_FLAG_ODD_SIZE with an odd W, H, uW or uH: exact trigonometric resampling on both axes (kernels_odd.hpp), up, down or
-    // -u 1; ncols = min(W, uW)/2 + 1 (floor); (rows + 1)/2 workgroups per plane in the row kernels
-    bool odd = false;
-    // fftup_plan_create_size: the output size is given per axis (always `odd`'s kernels, each axis up, down or equal on its own);
-    // align = FFTUP_ALIGN_CENTRE: phase tables of the axes whose lengths differ (kernels_odd.hpp), nullptr otherwise
-    bool exact = false;
-    uint32_t align = 0;
-    float2 *phW = nullptr, *phH = nullptr;
-    // fftup_plan_create_view: the frame's trigonometric interpolant at origin + m span / M per axis (kernels_view.hpp).  Buffers and
-    // the convolution lengths are sized for the worst case of W, H, uW, uH (kmax = N/2), so fftup_plan_set_view re-aims the plan in
-    // place; ncols = kmax_x + 1 and NT follow the CURRENT view.  Per axis: kmax, the smooth convolution length L with its roots,
-    // and the three chirp tables (view_tables.hpp)
-    bool view = false;
+    fftup_jit::Module* jit = nullptr;  // mixed == 3: the kernels specialised at plan time
+    struct FourTables { float2 *tw1 = nullptr, *tw2 = nullptr; };   // roots of the two factors of a four-step split (PlanGeometry::Four)
+    FourTables fourFtw, fourItw, colFtw, colItw;
+    BzPlan bzW{}, bzH{}, bzUW{}, bzUH{};        // per transform: L (PlanGeometry::bzL), its radix list and the tables of a Bluestein transform
+    float2 *phW = nullptr, *phH = nullptr;      // align = FFTUP_ALIGN_CENTRE: phase tables of the axes whose lengths differ, nullptr otherwise
+    // view plans: the current view; per axis kmax, the smooth convolution length L (PlanGeometry::viewL) with its roots, and the
+    // three chirp tables (view_tables.hpp)
     fftup_view vw{};
     struct ViewAxis { int kmax = 0; uint32_t L = 0; StagePlan planL{}; float2 *tw = nullptr, *pre = nullptr, *post = nullptr, *bhat = nullptr; };
     ViewAxis vx, vy;
-    int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
-    int pairs_per_strip = 6;
     bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
 
     // device memory
@@ -179,8 +127,10 @@ struct fftup_plan {
 
 // ---- fftup_plan.hip
 int dev_alloc(fftup_plan* P, void** ptr, size_t bytes);           // hipMalloc owned by the plan
-int lane_count();                                                 // FFTUP_STREAMS
-void set_strip_length(fftup_plan* P);
+inline DeviceFacts device_facts(const hipDeviceProp_t& prop)
+{
+    return {prop.sharedMemPerBlock ? prop.sharedMemPerBlock : 65536, prop.multiProcessorCount, prop.gcnArchName};
+}
 // the row kernel reads uint8 RGB directly (fp32 / fp16 plans only)
 inline bool fuse_u8(const fftup_plan* P) { return (P->cfg.flags & FFTUP_FLAG_FUSE_U8_LOAD) && !P->dbl; }
 inline int check_slot(fftup_plan* P, uint32_t slot)
@@ -191,10 +141,7 @@ inline int check_slot(fftup_plan* P, uint32_t slot)
 }
 
 // ---- fftup_launch.hip: everything that names a kernel (each instantiation once, in the selector of its pass and family)
-// facts about the kernels the planner needs (defined next to the kernels)
-int kernels_generic_max_threads(bool dbl);                        // threads per workgroup of the size-generic kernels
-int kernels_aot_mixed_plan(uint32_t W, uint32_t H);               // 1: 1920x1080, 2: 1280x720 (ahead-of-time mixed-radix plans), 0: none
-size_t kernels_tuned_col_lds(uint32_t H);                         // LDS bytes of the power-of-two column kernel
+// (the facts about the kernels the planner needs: plan_rules.hpp)
 int kernels_set_attributes(fftup_plan* P);                        // dynamic LDS sizes above 64 KB, for the kernels launch_frame's selectors give THIS plan
 // one frame on lane P->cur: `which` < 0 launches all of its kernels, 0..3 only that one, 22 = the pre-sharpen tap of a fused plan
 int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which);
