@@ -66,7 +66,7 @@ def _run(W, H, u, precision, flags, rgb=None, planes=None):
     return pre, out, names, desc
 
 
-def _check(W, H, u, precision, down, uint8, seed, tag):
+def _check(W, H, u, precision, down, uint8, seed, tag, pooled=None):
     """sc * R is the amplitude-preserving image y: sc = upsq for an upscale, (uW uH) / (W H) for a downscale"""
     import vkresample_amd as v
     rgb, planes, x = _inputs(W, H, precision, uint8, seed)
@@ -99,9 +99,13 @@ def _check(W, H, u, precision, down, uint8, seed, tag):
            out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
            out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
         assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert (pre != opre).mean() <= 0.01
-        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4 and (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4
         assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+        if pooled is None:
+            assert (pre != opre).mean() <= 0.01
+            assert (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
+            pooled.append((int((pre != opre).sum()), pre.size, int((out[:, :-1] != sh[:, :-1]).sum()), out[:, :-1].size))
     return pre, x
 
 
@@ -129,7 +133,10 @@ def test_anysize_parity_1366x768(precision, uint8):
     _check(1366, 768, 2.0, precision, False, uint8, 1366 + precision, "anysize p%d 1366x768 u2 u8%d" % (precision, uint8))
 
 
-@pytest.mark.parametrize("W,H,u,precision", [(124, 76, 0.5, 0), (124, 76, 0.5, 2), (2732, 1536, 0.5, 2)] + ([(2732, 1536, 0.5, 0)] if BIG else []))
+DOWN = [(124, 76, 0.5, 0), (124, 76, 0.5, 2), (2732, 1536, 0.5, 2)] + ([(2732, 1536, 0.5, 0)] if BIG else [])
+
+
+@pytest.mark.parametrize("W,H,u,precision", DOWN)
 @pytest.mark.parametrize("uint8", [False, True])
 def test_anysize_down_parity(W, H, u, precision, uint8):
     _check(W, H, u, precision, True, uint8, W + H + precision, "anysize_down p%d %dx%d u%.4g u8%d" % (precision, W, H, u, uint8))

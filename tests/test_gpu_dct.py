@@ -63,40 +63,54 @@ def _oracle(rgb, u, precision):
 SIZES_FP32 = [(64, 32, 2.0), (96, 60, 1.5), (640, 480, 2.0), (1920, 1080, 2.0), (840, 336, 1.25), (840, 336, 3.0), (16, 256, 2.0)]
 
 
+def _check(W, H, u, precision, fuse, seed, tag, pooled=None):
+    """one plan against the oracle at the bars above; `pooled`: a list that takes the -p 2 counts (differing, all) of R and of the
+    output in place of the two fraction bars (outputs of a few dozen values, tests/test_gpu_family_sweep.py)"""
+    import vkresample_amd as v
+    rgb = _frame(W, H, seed=seed)
+    pre, out = _run(rgb, u, precision, v.FLAG_FUSE_U8_LOAD if fuse else 0)
+    if precision == 0:
+        y, R = _oracle(rgb, u, 0)
+        assert pre.shape == y.shape
+        usq = D.upsq(u)
+        sh = O.sharpen(R, u, 0, 0.2)
+        _m(tag, pre_l2=_rel_l2(usq * pre, y), pre_max=np.abs(usq * pre - y).max(),
+           out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max())
+        assert _rel_l2(usq * pre, y) <= 2e-6
+        assert np.abs(usq * pre - y).max() <= 1e-5
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 5e-6
+        assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 2e-5
+    else:
+        _, opre = _oracle(rgb, u, 2)
+        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
+        sh = O.sharpen(opre, u, 2, 0.2)
+        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
+           out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
+           out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
+        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4
+        assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+        if pooled is None:
+            assert (pre != opre).mean() <= 0.01
+            assert (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        else:
+            pooled.append((int((pre != opre).sum()), pre.size, int((out[:, :-1] != sh[:, :-1]).sum()), out[:, :-1].size))
+    return pre, rgb
+
+
 @pytest.mark.parametrize("W,H,u", SIZES_FP32)
 @pytest.mark.parametrize("fuse", [False, True])
 def test_dct_fp32_parity(W, H, u, fuse):
-    import vkresample_amd as v
-    rgb = _frame(W, H, seed=W + H)
-    pre, out = _run(rgb, u, 0, v.FLAG_FUSE_U8_LOAD if fuse else 0)
-    y, R = _oracle(rgb, u, 0)
-    assert pre.shape == y.shape
-    usq = D.upsq(u)
-    sh = O.sharpen(R, u, 0, 0.2)
-    _m("dct_fp32 %dx%d u%g fuse%d" % (W, H, u, fuse), pre_l2=_rel_l2(usq * pre, y), pre_max=np.abs(usq * pre - y).max(),
-       out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max())
-    assert _rel_l2(usq * pre, y) <= 2e-6
-    assert np.abs(usq * pre - y).max() <= 1e-5
-    assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 5e-6
-    assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 2e-5
+    _check(W, H, u, 0, fuse, W + H, "dct_fp32 %dx%d u%g fuse%d" % (W, H, u, fuse))
 
 
-@pytest.mark.parametrize("W,H,u", [(64, 32, 2.0), (96, 60, 1.5), (640, 480, 2.0)])
+SIZES_FP16 = [(64, 32, 2.0), (96, 60, 1.5), (640, 480, 2.0)]
+
+
+@pytest.mark.parametrize("W,H,u", SIZES_FP16)
 @pytest.mark.parametrize("fuse", [False, True])
 def test_dct_fp16_parity(W, H, u, fuse):
-    import vkresample_amd as v
-    rgb = _frame(W, H, seed=3 * W + H)
-    pre, out = _run(rgb, u, 2, v.FLAG_FUSE_U8_LOAD if fuse else 0)
-    _, opre = _oracle(rgb, u, 2)
-    ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-    sh = O.sharpen(opre, u, 2, 0.2)
-    _m("dct_fp16 %dx%d u%g fuse%d" % (W, H, u, fuse), pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-       out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
-       out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
-    assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-    assert (pre != opre).mean() <= 0.01
-    assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4 and (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
-    assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+    _check(W, H, u, 2, fuse, 3 * W + H, "dct_fp16 %dx%d u%g fuse%d" % (W, H, u, fuse))
 
 
 def test_dct_ramp_has_no_border_ringing():

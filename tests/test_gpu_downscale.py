@@ -35,10 +35,11 @@ def _frame(W, H, seed=0, dist="N"):
     return synth.frame(seed, W, H, dist)
 
 
-def _scale(W, H, u, dct):
-    """y = scale * R"""
+def _scale(W, H, u, dct, half=False):
+    """y = scale * R (DCT mode: upsq as the plan holds it -- at -p 2 rounded to binary16, as in tests/test_gpu_dct.py; 0.5^2 and
+    0.75^2 are binary16 numbers, 0.4^2 is not)"""
     if dct:
-        return S.upsq(u)
+        return S.upsq(u, half)
     return S.out_size(W, u) * S.out_size(H, u) / (W * H)
 
 
@@ -66,13 +67,13 @@ def _inputs(W, H, precision, uint8, seed):
     return None, planes, planes.astype(np.float64)
 
 
-def _check(W, H, u, precision, dct, uint8, seed, tag):
+def _check(W, H, u, precision, dct, uint8, seed, tag, pooled=None):
     import vkresample_amd as v
     rgb, planes, x = _inputs(W, H, precision, uint8, seed)
     flags = (v.FLAG_DCT if dct else 0) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0)
     pre, out = _run(W, H, u, precision, flags, rgb, planes)
     uW, uH = S.out_size(W, u), S.out_size(H, u)
-    sc = _scale(W, H, u, dct)
+    sc = _scale(W, H, u, dct, precision == 2)
     y = S.dct_down_planes(x, uW, uH) if dct else S.fft_down_planes(x, uW, uH)
     assert pre.shape == y.shape == (3, uH, uW)
     R = y / sc
@@ -92,9 +93,13 @@ def _check(W, H, u, precision, dct, uint8, seed, tag):
            out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
            out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
         assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert (pre != opre).mean() <= 0.01
-        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4 and (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4
         assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+        if pooled is None:
+            assert (pre != opre).mean() <= 0.01
+            assert (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
+            pooled.append((int((pre != opre).sum()), pre.size, int((out[:, :-1] != sh[:, :-1]).sum()), out[:, :-1].size))
 
 
 # 16x512 -u 0.5: a thin frame whose column pass (512 points, tiles of 8) needs 69 648 bytes of dynamic LDS -- above the 64 KB a
@@ -113,7 +118,12 @@ def test_fft_down_parity_8k():
     _check(7680, 4320, 0.5, 0, False, True, 11, "down_fft p0 7680x4320 u0.5 u8")
 
 
-@pytest.mark.parametrize("W,H,u", [(96, 60, 0.5), (640, 480, 0.75), (1920, 1080, 0.5)])
+# 90x70 -u 0.8: found by tests/test_gpu_family_sweep.py -- a factor whose upsq = "%f"(u u) is no binary16 number: at -p 2 the plan
+# divides by the rounded constant (R = y / upsq, the constant of the sharpen pass), and _scale above has to as well
+SIZES_DCT = [(96, 60, 0.5), (640, 480, 0.75), (1920, 1080, 0.5), (90, 70, 0.8)]
+
+
+@pytest.mark.parametrize("W,H,u", SIZES_DCT)
 @pytest.mark.parametrize("precision", [0, 2])
 def test_dct_down_parity(W, H, u, precision):
     _check(W, H, u, precision, True, precision == 0, 3 * W + H, "down_dct p%d %dx%d u%.4g" % (precision, W, H, u))

@@ -52,7 +52,7 @@ def _run(W, H, uW, uH, precision, flags, align, rgb=None, planes=None):
     return pre, out, names, desc
 
 
-def _check(W, H, uW, uH, precision, extra, align, uint8, seed, tag):
+def _check(W, H, uW, uH, precision, extra, align, uint8, seed, tag, pooled=None):
     import vkresample_amd as v
     rgb, planes, x = _inputs(W, H, precision, uint8, seed)
     pre, out, names, desc = _run(W, H, uW, uH, precision, _flags(v, extra) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0), align, rgb, planes)
@@ -80,9 +80,13 @@ def _check(W, H, uW, uH, precision, extra, align, uint8, seed, tag):
            out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
            out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
         assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert (pre != opre).mean() <= 0.01
-        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4 and (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4
         assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+        if pooled is None:
+            assert (pre != opre).mean() <= 0.01
+            assert (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
+            pooled.append((int((pre != opre).sum()), pre.size, int((out[:, :-1] != sh[:, :-1]).sum()), out[:, :-1].size))
     return pre, x
 
 

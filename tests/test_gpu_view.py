@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import exactsize_oracle as E
+import family_sweep_cases as F
 import oraclelib as O
 import view_oracle as V
 from test_gpu_dct import _png_read, _png_write
@@ -52,14 +53,17 @@ def _run(W, H, uW, uH, origin, span, precision, flags, rgb=None, planes=None):
     return pre, out, names, desc
 
 
-def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag, y=None, dense=True):
+def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag, y=None, dense=True, pooled=None):
     """as tests/test_gpu_exactsize.py::_check; `y`: the amplitude-preserving image by another oracle (a function of the planes),
-    compared with the dense statement as well -- or, with dense=False (lengths of thousands), in its place"""
+    compared with the dense statement as well -- or, with dense=False (lengths of thousands), in its place; `pooled`: a list that
+    takes the -p 2 counts (differing, all) of R and of the output in place of the two fraction bars"""
     import vkresample_amd as v
     rgb, planes, x = _inputs(W, H, precision, uint8, seed)
     pre, out, names, desc = _run(W, H, uW, uH, origin, span, precision, _flags(v, extra) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0), rgb, planes)
     assert names[0] in ("row_r2c_odd", "row_r2c_odd_bz") and names[1] in ("col_view", "col_view_bz") and names[2:] == ["row_view_c2r", "sharpen"], names
-    assert ("_bz" in names[0]) == ("any" in extra), names
+    # (a Bluestein forward transform per axis whose input length is not smooth: FLAG_ANY_SIZE allows it, the lengths decide)
+    assert ("_bz" in names[0]) == (not F.smooth(W)) and ("_bz" in names[1]) == (not F.smooth(H)), names
+    assert "any" in extra or (F.smooth(W) and F.smooth(H))
     assert "rows %d->%d" % (W, uW) in desc and "columns %d->%d" % (H, uH) in desc and "origin" in desc and "span" in desc, desc
     sc = uW * uH / (span[0] * span[1])
     yv = V.view_planes(x, uW, uH, origin, span) if dense else y(x)
@@ -84,9 +88,13 @@ def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag, y=Non
            out_l2=_rel_l2(out[:, :-1], sh[:, :-1]), out_max=np.abs(out[:, :-1] - sh[:, :-1]).max(),
            out_diff_frac=(out[:, :-1] != sh[:, :-1]).mean())
         assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert (pre != opre).mean() <= 0.01
-        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4 and (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        assert _rel_l2(out[:, :-1], sh[:, :-1]) <= 3.5e-4
         assert np.abs(out[:, :-1] - sh[:, :-1]).max() <= 8e-3
+        if pooled is None:
+            assert (pre != opre).mean() <= 0.01
+            assert (out[:, :-1] != sh[:, :-1]).mean() <= 0.02
+        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
+            pooled.append((int((pre != opre).sum()), pre.size, int((out[:, :-1] != sh[:, :-1]).sum()), out[:, :-1].size))
     return pre, x
 
 

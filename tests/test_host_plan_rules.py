@@ -35,15 +35,14 @@ answers first, and a factor below 1 always shrinks), "row too long: no four-step
 import ctypes as C
 import json
 import os
-import subprocess
 
 import pytest
 
+import plan_driver
 from vkresample_amd import _lib
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def _rows(name):
@@ -101,25 +100,12 @@ def test_error_table_reaches_every_rule():
 @pytest.fixture(scope="module")
 def driver_lines(tmp_path_factory):
     """the driver, linked from the library's own object files (plan_rules, the kernel facts of fftup_launch, the chooser of jit),
-    run once over every request of plan_geometry.json"""
+    run once over every request of plan_geometry.json (tests/plan_driver.py)"""
     d = tmp_path_factory.mktemp("plan_rules")
-    exe = str(d / "plan_rules_driver")
-    obj = os.path.join(ROOT, "build", "obj")
-    objs = sorted(os.path.join(obj, f) for f in os.listdir(obj) if f.endswith(".o") and f != "jit_knobs.o")
-    subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "vkresample_amd", "csrc"),
-                           "-x", "hip", os.path.join(ROOT, "tests", "plan_rules_driver.cpp"), "-x", "none"] + objs + ["-o", exe])
     g = _rows("plan_geometry.json")
-    dev = g["device"]
-    lines = ["device %d %d %s" % (dev["lds_bytes"], dev["compute_units"], dev["arch"])]
-    for r in g["rows"]:
-        lines.append(" ".join([r["entry"], str(r["width"]), str(r["height"]), float(r["upscale"]).hex(), str(r["precision"]), str(r["flags"]), str(r["ring"]),
-                               str(r["out"][0]), str(r["out"][1]), str(r["align"])] + [float(x).hex() for x in r["view"]]))
-    env = {k: v for k, v in os.environ.items() if k not in ("FFTUP_EXPERIMENT", "FFTUP_JIT", "FFTUP_STREAMS")}
-    env["FFTUP_CACHE_DIR"] = str(d / "empty_cache")
-    p = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, env=env)
-    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
-    out = p.stdout.splitlines()
-    assert len(out) == len(g["rows"])
+    lines = [plan_driver.request_line(r["entry"], r["width"], r["height"], r["upscale"], r["precision"], r["flags"], r["ring"], r["out"], r["align"],
+                                      r["view"]) for r in g["rows"]]
+    out = plan_driver.run(plan_driver.build(d), d, lines)
     return dict(zip([r["name"] for r in g["rows"]], out))
 
 
