@@ -251,7 +251,7 @@ static void sharpen_plane(const double* R, const double* Rim, double* out, uint3
                     uint64_t f = (uint64_t)xs[b] + (uint64_t)ys[a] * uW;   /* index(): x + y*stride */
                     /* Reads at/after the end of the plane's written data hit the 2*uH padding
                      * elements = stale memory in the reference (quirk B5).  Defined here as
-                     * "same column, last written row"; the last row is excluded from parity. */
+                     * "same column, last written row": the HIP path is held to this on the last row too. */
                     while (f >= plane) f -= uW;
                     double t = RQ(upsq * R[f]);            /* tex = upscale * inputs[...]      */
                     double l = fabs(t);                     /* length(scalar)                   */

@@ -119,6 +119,20 @@ def upscale_rgb8(rgb, upscale=2.0, precision=0, sharpen=0.2, u8_wrap=0):
     return pre, out, rgb_out
 
 
+def presharpen_rgb8(rgb, upscale=2.0, precision=0):
+    """rgb: [H][W][3] uint8 -> the pre-sharpen image alone (no sharpen pass: at -p 2 the oracle's binary16 sharpen is the slow part)"""
+    rgb = np.ascontiguousarray(rgb, dtype=np.uint8)
+    H, W, _ = rgb.shape
+    cfg = _cfg(W, H, upscale, precision)
+    uW, uH = out_dims(W, H, upscale)
+    _fit_threads(uW * uH)
+    pre = np.empty((3, uH, uW))
+    rc = lib().orc_upscale_rgb8(C.byref(cfg), rgb.ctypes.data_as(C.c_void_p), pre.ctypes.data_as(C.c_void_p), None, None)
+    if rc:
+        raise ValueError("oracle rc=%d" % rc)
+    return pre
+
+
 def sharpen(R, upscale=2.0, precision=0, sharpen=0.2):
     R = np.ascontiguousarray(R, dtype=np.float64)
     _, uH, uW = R.shape

@@ -35,7 +35,7 @@ def test_cli_single_image_1080p(tmp_path):
     assert "Thread 0 finished." in r.stdout and "Total time:" in r.stdout
     out = _png_read(tmp_path / "1920_3840_upscaled.png")
     _, _, ou8 = O.upscale_rgb8(rgb, 2.0, 0, 0.2)
-    d = np.abs(out[:-1].astype(int) - ou8[:-1].astype(int))
+    d = np.abs(out.astype(int) - ou8.astype(int))
     assert out.shape == (2160, 3840, 3) and d.max() <= 1 and (d != 0).mean() <= 5e-3
 
 
@@ -52,7 +52,7 @@ def test_cli_upscale_factor_as_a_ratio(tmp_path):
         outs.append(_png_read(tmp_path / "out.png"))
     assert outs[0].shape == (720, 1280, 3) and np.array_equal(outs[0], outs[1])
     _, _, ou8 = O.upscale_rgb8(rgb, float(np.float32(4.0 / 3.0)), 0, 0.2)
-    d = np.abs(outs[0][:-1].astype(int) - ou8[:-1].astype(int))
+    d = np.abs(outs[0].astype(int) - ou8.astype(int))
     assert d.max() <= 1 and (d != 0).mean() <= 5e-3
 
 
@@ -69,7 +69,7 @@ def test_cli_sizes_specialised_at_plan_time(tmp_path, W, H, u, p):
     assert re.search(r"VkResample %.1fx upscale: %dx%d to %dx%d Time: [0-9.]+ ms" % (float(u), W, H, uW, uH), r.stdout)
     out = _png_read(tmp_path / "out.png")
     _, _, ou8 = O.upscale_rgb8(rgb, float(u), int(p), 0.2)
-    d = np.abs(out[:-1].astype(int) - ou8[:-1].astype(int))
+    d = np.abs(out.astype(int) - ou8.astype(int))
     assert out.shape == (uH, uW, 3)
     if p == "0":
         assert d.max() <= 1 and (d != 0).mean() <= 5e-3
@@ -108,7 +108,7 @@ def test_cli_config1_literal_image(tmp_path):
     out = _png_read(tmp_path / "up.png")
     _, _, ou8 = O.upscale_rgb8(d["rgb"], 2.0, 0, 0.2)
     assert np.array_equal(ou8[1000:1064, 1800:1864], d["u8_crop"])
-    dd = np.abs(out[:-1].astype(int) - ou8[:-1].astype(int))
+    dd = np.abs(out.astype(int) - ou8.astype(int))
     assert out.shape == (2160, 3840, 3) and dd.max() <= 1 and (dd != 0).mean() <= 5e-3
 
 
@@ -126,7 +126,7 @@ def test_cli_batched_two_threads(tmp_path):
     for k, f in enumerate(frames):
         out = _png_read(tmp_path / "outp" / ("%06d.png" % (k + 1)))
         _, _, ou8 = O.upscale_rgb8(f, 2.0, 2, 0.1)
-        d = np.abs(out[:-1].astype(int) - ou8[:-1].astype(int))
+        d = np.abs(out.astype(int) - ou8.astype(int))
         assert d.max() <= 2 and (d > 1).mean() <= 1e-3          # fp16 storage: a one-ulp flip can move a code by 2
 
 
@@ -150,7 +150,7 @@ def test_cli_batched_work_queue(tmp_path, threads, extra):
         a = _png_read(tmp_path / "oq" / ("%06d.png" % (k + 1)))
         assert np.array_equal(a, _png_read(tmp_path / "os" / ("%06d.png" % (k + 1)))), k
         _, _, ou8 = O.upscale_rgb8(f, 2.0, 0, 0.2)
-        d = np.abs(a[:-1].astype(int) - ou8[:-1].astype(int))
+        d = np.abs(a.astype(int) - ou8.astype(int))
         assert d.max() <= 1 and (d != 0).mean() <= 5e-3
 
 
@@ -177,7 +177,7 @@ def test_cli_batched_threads_share_the_plan_of_their_size(tmp_path):
         for k, f in enumerate(fr):
             a = _png_read(tmp_path / folder / ("%06d.png" % (k + 1)))
             _, _, ou8 = O.upscale_rgb8(f, 2.0, 0, 0.2)
-            d = np.abs(a[:-1].astype(int) - ou8[:-1].astype(int))
+            d = np.abs(a.astype(int) - ou8.astype(int))
             assert a.shape == ou8.shape and d.max() <= 1 and (d != 0).mean() <= 5e-3, (folder, k)
 
 
@@ -218,7 +218,7 @@ def test_cli_batched_queue_one_thread_and_missing_file(tmp_path):
         b = _png_read(tmp_path / "o3" / ("%06d.png" % (k + 1)))
         assert np.array_equal(a, b), k
         _, _, ou8 = O.upscale_rgb8(f, 2.0, 0, 0.2)
-        d = np.abs(a[:-1].astype(int) - ou8[:-1].astype(int))
+        d = np.abs(a.astype(int) - ou8.astype(int))
         assert d.max() <= 1 and (d != 0).mean() <= 5e-3
     os.remove(tmp_path / "inp" / "000005.png")
     r = subprocess.run(base + ["-ofolder", "o4"], capture_output=True, text=True, cwd=tmp_path)
@@ -235,7 +235,7 @@ def test_cli_double_precision(tmp_path):
     assert r.returncode == 0, r.stdout + r.stderr
     out = _png_read(tmp_path / "out.png")
     _, _, ou8 = O.upscale_rgb8(rgb, 2.0, 1, 0.2)
-    d = np.abs(out[:-1].astype(int) - ou8[:-1].astype(int))
+    d = np.abs(out.astype(int) - ou8.astype(int))
     assert out.shape == (252, 480, 3) and d.max() <= 1 and (d != 0).mean() <= 1e-4
 
 

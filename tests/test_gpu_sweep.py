@@ -107,21 +107,21 @@ def _sweep_case(W, H, u, p, flags, sharpen, seed, expect_specialised=False):
     opre, oout, ou8 = O.upscale_rgb8(rgb, u, p, sharpen)
     # the 8-bit image: trunc(255 x) can flip by one code on a float error (for u = 1 every exact value sits ON a code boundary);
     # -p 2: one binary16 ulp near 1.0 is a quarter of a code
-    d8o = np.abs(u8_planes[:-1].astype(int) - ou8[:-1].astype(int))
+    d8o = np.abs(u8_planes.astype(int) - ou8.astype(int))
     assert d8o.max() <= (1 if p != 2 else 2), int(d8o.max())
     scale = 1.0 / (np.float32(u) * np.float32(u))                      # the pre-sharpen image is g / u^2
     if p == 1:
         assert np.abs(pre - opre).max() <= 1e-12
-        assert np.abs(out[:, :-1] - oout[:, :-1]).max() <= 1e-7      # sqrt(min) has unbounded slope at 0 (see the fp32 test)
+        assert np.abs(out - oout).max() <= 1e-7      # sqrt(min) has unbounded slope at 0 (see the fp32 test)
     elif p == 0:
         # (ten times what the full-size tests measure; uniform-noise frames and small sharpen factors: the filter's sqrt slope)
         assert np.abs(pre - opre).max() <= 1e-5 * scale * 4 and np.linalg.norm(pre - opre) <= 3e-6 * np.linalg.norm(opre)
-        assert np.abs(out[:, :-1] - oout[:, :-1]).max() <= 5e-4
+        assert np.abs(out - oout).max() <= 5e-4
         # u = 1: the transform pair reproduces the 8-bit input, so every black pixel is EXACTLY 0 in the fp64 oracle and +-1e-7 on the
         # device -- the filter's sqrt(min / ..) turns that into ~3e-4 at every pixel with a black neighbour (max bound above still
         # holds); a 400-case run with another seed measured 2.35e-5 on four such cases (profiles/r03_z_sweep_400.txt)
-        assert np.linalg.norm(out[:, :-1] - oout[:, :-1]) <= (5e-5 if u == 1.0 else 2e-5) * np.linalg.norm(oout[:, :-1])
+        assert np.linalg.norm(out - oout) <= (5e-5 if u == 1.0 else 2e-5) * np.linalg.norm(oout)
     else:
         ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
         assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert np.abs(out[:, :-1] - oout[:, :-1]).max() <= 1.6e-2 and np.linalg.norm(out[:, :-1] - oout[:, :-1]) <= 2e-3 * np.linalg.norm(oout[:, :-1])
+        assert np.abs(out - oout).max() <= 1.6e-2 and np.linalg.norm(out - oout) <= 2e-3 * np.linalg.norm(oout)

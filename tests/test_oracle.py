@@ -253,7 +253,7 @@ def test_complex_path_half_memory():
     const = np.full((H, W, 3), 77, np.uint8)
     pre, out, u8 = O.upscale_rgb8(const, 2.0, 2, 0.2)
     cval = float(np.float16(np.float64(np.float32(np.float16(77))) / 255.0))
-    assert np.abs(pre * 4 - cval).max() <= 2.0 ** -11 and np.ptp(out[:, :-1]) == 0.0 and np.all(u8[:-1] == u8[0, 0])
+    assert np.abs(pre * 4 - cval).max() <= 2.0 ** -11 and np.ptp(out) == 0.0 and np.all(u8 == u8[0, 0])
     rgb = rng.integers(0, 256, (H, W, 3), dtype=np.uint8)
     pre, out, _ = O.upscale_rgb8(rgb, 2.0, 2, 0.2)
     assert np.array_equal(pre, pre.astype(np.float16).astype(np.float64)) and np.array_equal(out, out.astype(np.float16).astype(np.float64))
@@ -444,7 +444,7 @@ def test_x_split_identities_of_the_u2_inverse(W, H):
     uW = 2 * W
     k = np.arange(W // 2 + 1)
     for c in range(3):
-        for r in range(2 * H - 1):                           # (the last output row is excluded from parity everywhere: quirk B5)
+        for r in range(2 * H):
             Z = np.fft.rfft(pre[c, r])                       # the row's spectrum: kx = 0..uW/2, zero beyond W/2
             assert np.abs(Z[W // 2 + 1:]).max() <= 1e-12
             Xe = Z[:W // 2 + 1].copy()
@@ -458,3 +458,10 @@ def test_x_split_identities_of_the_u2_inverse(W, H):
         assert np.abs(res - res[:, :1]).max() <= 1e-12      # one constant per even row ...
         s_nyq = (x[c] * ((-1.0) ** np.arange(H))[:, None]).sum()          # S[H/2, 0]
         assert np.abs(np.abs(res[:, 0]) - abs(s_nyq) / (W * H)).max() <= 1e-12 and np.abs(res[0::2, 0] + res[1::2, 0]).max() <= 1e-12   # ... +- S[H/2,0] / WH, alternating
+
+
+@pytest.mark.parametrize("precision", [0, 1, 2])
+def test_presharpen_alone_is_the_full_run_s_pre_sharpen_image(precision):
+    """oraclelib.presharpen_rgb8 (the transforms without the sharpen pass) against the full run"""
+    rgb = np.random.default_rng(8).integers(0, 256, (12, 20, 3), dtype=np.uint8)
+    assert np.array_equal(O.presharpen_rgb8(rgb, 2.0, precision), O.upscale_rgb8(rgb, 2.0, precision)[0])
