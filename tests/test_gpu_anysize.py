@@ -1,6 +1,7 @@
-"""GPU: FFTUP_FLAG_ANY_SIZE (csrc/kernels_bluestein.hpp) -- sizes with a prime factor above 7 -- against the fp64 statement of the
-reference's filter at that size: oracle/ref_layout_emulation.closed_form (quirks B1-B3) followed by oraclelib.sharpen (B4, B5); for
-FFTUP_FLAG_DOWNSCALE plans tests/downscale_oracle.py.
+"""GPU: FFTUP_FLAG_ANY_SIZE (csrc/kernels_bluestein.hpp; Bluestein forward rows: k_row_r2c_odd of csrc/kernels_odd.hpp) -- sizes with
+a prime factor above 7 -- against the fp64 statement of the reference's filter at that size:
+oracle/ref_layout_emulation.closed_form (quirks B1-B3) followed by oraclelib.sharpen (B4, B5); for FFTUP_FLAG_DOWNSCALE plans
+tests/downscale_oracle.py.
 
 Bars: the project's, as stated at the top of tests/test_gpu_downscale.py.  fp32: the pre-sharpen image y = upsq R within relative L2
 2e-6 and max 1e-5 of full scale; the sharpened output against oraclelib.sharpen applied to the oracle's R within relative L2 5e-6

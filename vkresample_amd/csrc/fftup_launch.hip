@@ -90,15 +90,13 @@ template <class F> static auto with_mixed_cfg(const fftup_plan* P, F&& f) { retu
 
 // ---- the selectors.  `kind`: the input kind of the frame (1 planes, 2 8-bit RGB).  A selector returns the kernel -- except
 // where the kernels of one pass differ in their trailing arguments (the Bluestein forms take their BzPlans after the parameter
-// struct), so that no single Kern type holds them: generic_row_kernel, generic_c2r_kernel and columns_kernel call
+// struct), so that no single Kern type holds them: generic_c2r_kernel and columns_kernel call
 // f(kernel, the arguments after the parameter struct...) instead, and launch and attribute setter pass their action as f.
-// size-generic R2C plans, fp32 / fp16 (kernels_generic.hpp; a Bluestein transform on the axis: kernels_bluestein.hpp)
-template <class F> static auto generic_row_kernel(const fftup_plan* P, int kind, F&& f)
+// size-generic R2C plans, fp32 / fp16 (kernels_generic.hpp; a Bluestein transform on the axis: kernels_bluestein.hpp, and for
+// the forward rows the resampling row kernel -- resampling_rows below)
+static Kern<RowR2CParams> generic_row_kernel(const fftup_plan* P, int kind)
 {
-    return with_mode(P->half, kind, [&](auto m) {
-        if (P->bzW.L) return f(kern(k_row_r2c_bz<m()>, P->thrW, P->ldsRowF), P->bzW);
-        return f(kern(k_row_r2c<m()>, P->thrW, P->ldsRowF));
-    });
+    return with_mode(P->half, kind, [&](auto m) { return kern(k_row_r2c<m()>, P->thrW, P->ldsRowF); });
 }
 // (also the inverse rows of an FFT downscale plan)
 template <class F> static auto generic_c2r_kernel(const fftup_plan* P, F&& f)
@@ -194,13 +192,17 @@ static Kern<DownColParams> crop_col_kernel(const fftup_plan* P)
 {
     return with_flag(P->bzH.L || P->bzUH.L, [&](auto bz) { return with_tile(P->TK, [&](auto tk) { return kern(k_col_crop<tk(), bz()>, P->thrCol, P->ldsCol); }); });
 }
-// FFTUP_FLAG_ODD_SIZE / fftup_plan_create_size (kernels_odd.hpp); the forward rows of fftup_plan_create_view are theirs
+// the resampling kernels (kernels_odd.hpp): FFTUP_FLAG_ODD_SIZE / fftup_plan_create_size; the forward rows of fftup_plan_create_view
+// and the Bluestein forward rows of a size-generic plan
 static Kern<OddRowParams> odd_row_kernel(const fftup_plan* P, int kind)
 {
     return with_mode(P->half, kind, [&](auto m) { return kern(k_row_r2c_odd<m()>, P->thrW, P->ldsRowF); });
 }
 static Kern<OddColParams> odd_col_kernel(const fftup_plan* P) { return with_tile(P->TK, [&](auto tk) { return kern(k_col_odd<tk()>, P->thrCol, P->ldsCol); }); }
 static Kern<OddC2RParams> odd_c2r_kernel(const fftup_plan* P) { return with_flag(P->half, [&](auto h) { return kern(k_row_c2r_odd<h()>, P->thrUW, P->ldsRowI); }); }
+// the forward rows of a size-generic plan run the resampling row kernel when they are Bluestein transforms (what the attribute
+// setter allows and what launch_frame_generic launches: both ask here)
+static bool resampling_rows(const fftup_plan* P) { return P->family == Family::generic && P->bzW.L != 0; }
 // fftup_plan_create_view (kernels_view.hpp)
 static Kern<ViewColParams> view_col_kernel(const fftup_plan* P) { return with_tile(P->TK, [&](auto tk) { return kern(k_col_view<tk()>, P->thrCol, P->ldsCol); }); }
 static Kern<ViewC2RParams> view_c2r_kernel(const fftup_plan* P) { return with_flag(P->half, [&](auto h) { return kern(k_row_view_c2r<h()>, P->thrUW, P->ldsRowI); }); }
@@ -299,7 +301,7 @@ int kernels_set_attributes(fftup_plan* P)
     AllowLds allow;
     switch (P->family) {
     case Family::generic:
-        for (int kind : {1, 2}) generic_row_kernel(P, kind, allow);
+        for (int kind : {1, 2}) { if (resampling_rows(P)) allow(odd_row_kernel(P, kind)); else allow(generic_row_kernel(P, kind)); }
         allow_columns<float2>(P, allow);
         generic_c2r_kernel(P, allow);
         break;
@@ -312,7 +314,7 @@ int kernels_set_attributes(fftup_plan* P)
     case Family::tuned: allow(tuned_col_kernel(P)); allow(fused_kernel(P)); break;          // (rows: static LDS)
     case Family::mixed_aot: allow(mixed_col_kernel(P)); allow(mixed_c2r_kernel(P)); allow(fused_kernel(P)); break;
     case Family::mixed_jit:           // (a plan-time plan without a row factorization runs the size-generic row kernel)
-        if (P->jit->choice.row_kind == 2) for (int kind : {1, 2}) generic_row_kernel(P, kind, allow);
+        if (P->jit->choice.row_kind == 2) for (int kind : {1, 2}) allow(generic_row_kernel(P, kind));
         break;
     }
     if (allow.err != hipSuccess) return fail(FFTUP_E_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(allow.err));
@@ -497,7 +499,8 @@ static void down_inv(fftup_plan* P, hipStream_t st)
 // ---- FFTUP_FLAG_ODD_SIZE with an odd length: row R2C keeping kx <= min(W, uW)/2 -> column forward / bin map / inverse -> row C2R ->
 // sharpen (kernels_odd.hpp).  Up, down or -u 1; (rows + 1) / 2 workgroups per plane, the last one with a single row when odd.
 // Plans of fftup_plan_create_size run the same four launches, each axis with its own direction, centre-aligned ones with phase tables.
-// fftup_plan_create_view runs the same row R2C keeping kx <= kmax_x, without fold or phase table.
+// fftup_plan_create_view runs the same row R2C keeping kx <= kmax_x, without fold or phase table.  Size-generic plans with
+// Bluestein forward rows run it too: kmax = W/2 (uW >= W), no fold, P->phW == nullptr.
 static void odd_rows(fftup_plan* P, uint32_t in_slot, int kind, hipStream_t st)
 {
     const bool view = P->family == Family::view;
@@ -700,7 +703,7 @@ static int launch_frame_tuned(fftup_plan* P, uint32_t in_slot, uint32_t out_slot
     return frame_status();
 }
 
-// ---- the size-generic R2C plans on fp32 / fp16 data (kernels_generic.hpp; FFTUP_FLAG_ANY_SIZE: kernels_bluestein.hpp) and the
+// ---- the size-generic R2C plans on fp32 / fp16 data (kernels_generic.hpp; FFTUP_FLAG_ANY_SIZE: kernels_bluestein.hpp, odd_rows) and the
 // mixed-radix plans: ahead of time (kernels_mixed.hpp) or specialised at plan time -- those are launched from P->jit as it is NOW
 // (the tuner swaps it after plan creation)
 static int launch_frame_generic(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
@@ -712,7 +715,8 @@ static int launch_frame_generic(fftup_plan* P, uint32_t in_slot, uint32_t out_sl
     auto keep_first = [&](hipError_t e) { if (jerr == hipSuccess) jerr = e; };       // (later launches must not mask an earlier failure)
     if (which < 0 || which == 0) {
         const dim3 grid(P->H / 2, 3);
-        if (aot || (jit && P->jit->choice.row_kind != 2)) {
+        if (resampling_rows(P)) odd_rows(P, in_slot, kind, st);
+        else if (aot || (jit && P->jit->choice.row_kind != 2)) {
             RowR2CTParams q{};
             q.S1 = P->lanes[P->cur].S1; q.tw = P->twW; q.H = (int)P->H; q.NT = P->NT;
             set_in(P, in_slot, kind, q);
@@ -723,7 +727,7 @@ static int launch_frame_generic(fftup_plan* P, uint32_t in_slot, uint32_t out_sl
             p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
             p.TK = P->TK; p.NT = P->NT;
             set_in(P, in_slot, kind, p);
-            generic_row_kernel(P, kind, [&](auto k, const auto&... z) { launch(k, grid, st, p, z...); });
+            launch(generic_row_kernel(P, kind), grid, st, p);
         }
     }
     if ((which < 0 || which == 1) && (jit || aot)) {

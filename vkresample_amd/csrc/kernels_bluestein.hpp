@@ -12,9 +12,10 @@
 // radians -- formed in fp32 it is off by ~1e-3 rad at N of a few thousand; tests/test_host_anysize.py keeps the comparison), and
 // are read from global memory (at most 64 KB per length: L2 resident).
 //
-// The kernels below are the size-generic row R2C, column and row C2R kernels of kernels_generic.hpp -- same parameters, same
-// spectrum layout, same packing / unpacking / shift / read-guard code around the transforms -- with every transform chosen PER
-// TRANSFORM: Bluestein where its BzPlan says so (L != 0), fft_lds where the length is smooth.  Buffers are sized by L * TK.
+// The kernels below are the size-generic column and row C2R kernels of kernels_generic.hpp -- same parameters, same spectrum
+// layout, same unpacking / shift / read-guard code around the transforms -- with every transform chosen PER TRANSFORM: Bluestein
+// where its BzPlan says so (L != 0), fft_lds where the length is smooth.  Buffers are sized by L * TK.  (Bluestein rows of the
+// forward pass run k_row_r2c_odd, kernels_odd.hpp: its unpack is the size-generic one.)
 // They live here and not behind a template flag in kernels_generic.hpp because that file is part of the sources the plan-time
 // compiler embeds and the committed counter profiles are fingerprinted on (bench.py kernel_sources_sha256): plans that are valid
 // without the flag keep their kernels, binaries and fingerprints byte for byte.  fp32 arithmetic only (no -p 1 Bluestein plans).
@@ -59,32 +60,37 @@ __device__ __forceinline__ float2* fft_any(float2* a, float2* b, const StagePlan
     return fft_lds<DIR, TK>(a, b, P, tw, tid, T);
 }
 
-// k_row_r2c with a Bluestein transform of the rows.  grid (H/2, 3); dynamic LDS = 2 * lpad_size(z.L) complex
-template <int MODE>
-__global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_r2c_bz(RowR2CParams p, BzPlan z)
+// ---- what the column and inverse row kernels here, in kernels_downscale.hpp, kernels_odd.hpp and kernels_view.hpp share
+// one tile of a blocked half spectrum, `rows` rows of TK columns at `src`, into LDS; the columns the spectrum does not have as zeros
+template <int TK>
+__device__ __forceinline__ void load_col_tile(float2* a, const float2* src, int rows, int ncol_valid, int tid, int T)
 {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float2* a = (float2*)smem;
-    float2* b = a + lpad_size(z.L);
-    const int tid = threadIdx.x, T = blockDim.x;
-    const int j = blockIdx.x, c = blockIdx.y;
-    const int W = p.W;
-    for (int n = tid; n < W; n += T)
-        a[lpad(n)] = make_float2((float)load_px<MODE>(p, c, 2 * j, n), (float)load_px<MODE>(p, c, 2 * j + 1, n));
-    __syncthreads();
-    const float2* Z = fft_bluestein<+1, 1>(a, b, W, z, tid, T);
-    // unpack two real rows as k_row_r2c (vkFFT.h:4292-4323)
-    const long tile_stride = (long)p.H * p.TK;
-    float2* base = p.S1 + (long)c * p.NT * tile_stride;
-    for (int k = tid; k <= W / 2; k += T) {
-        const float2 zk = Z[lpad(k)];
-        const float2 zn = Z[lpad(k == 0 ? 0 : W - k)];
-        const float2 A = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y - zn.y));
-        const float2 B = make_float2(0.5f * (zk.y + zn.y), 0.5f * (-zk.x + zn.x));
-        float2* dst = base + (long)(k / p.TK) * tile_stride + (long)(2 * j) * p.TK + (k % p.TK);
-        dst[0] = A;
-        dst[p.TK] = B;
+    for (int e = tid; e < rows * TK; e += T) {
+        float2 v = make_float2(0.f, 0.f);
+        if ((e % TK) < ncol_valid) v = src[e];
+        a[lpad(e)] = v;
     }
+}
+// ... and back: the columns that exist, as they are or times `s`
+template <int TK>
+__device__ __forceinline__ void store_col_tile(float2* dst, const float2* D, int rows, int ncol_valid, int tid, int T)
+{
+    for (int e = tid; e < rows * TK; e += T)
+        if ((e % TK) < ncol_valid) dst[e] = D[lpad(e)];
+}
+template <int TK>
+__device__ __forceinline__ void store_col_tile(float2* dst, const float2* D, int rows, int ncol_valid, float s, int tid, int T)
+{
+    for (int e = tid; e < rows * TK; e += T)
+        if ((e % TK) < ncol_valid) dst[e] = cscale(D[lpad(e)], s);
+}
+// element n of the row that starts at element `row` of the dense image R[3][uH][uW], fp32 or binary16.  (The inverse row kernels
+// store one element at a time: with an odd uW the second row of a pair is not 4-byte aligned as binary16)
+template <bool HALF_OUT>
+__device__ __forceinline__ void store_px(void* R, long row, int n, float v)
+{
+    if constexpr (HALF_OUT) ((__half*)R + row)[n] = __float2half_rn(v);
+    else ((float*)R + row)[n] = v;
 }
 
 // k_col (two-buffer form) with either transform Bluestein.  grid (NT, 3); dynamic LDS = 2 * lpad_size(nbuf * TK) complex,
@@ -99,12 +105,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_bz(Col
     const int tile = blockIdx.x, c = blockIdx.y;
     const int H = p.H, uH = p.uH;
     const int ncol_valid = min(TK, p.ncols - tile * TK);
-    const float2* src = p.S1 + ((long)c * p.NT + tile) * H * TK;
-    for (int e = tid; e < H * TK; e += T) {
-        float2 v = make_float2(0.f, 0.f);
-        if ((e % TK) < ncol_valid) v = src[e];
-        a[lpad(e)] = v;
-    }
+    load_col_tile<TK>(a, p.S1 + ((long)c * p.NT + tile) * H * TK, H, ncol_valid, tid, T);
     __syncthreads();
     float2* F = fft_any<+1, TK>(a, b, p.planH, p.twH, zH, tid, T);
     float2* G = (F == a) ? b : a;
@@ -120,9 +121,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_bz(Col
     }
     __syncthreads();
     const float2* D = fft_any<-1, TK>(G, F, p.planUH, p.twUH, zUH, tid, T);
-    float2* dst = p.S2 + ((long)c * p.NT + tile) * uH * TK;
-    for (int e = tid; e < uH * TK; e += T)
-        if ((e % TK) < ncol_valid) dst[e] = cscale(D[lpad(e)], p.inv_norm);
+    store_col_tile<TK>(p.S2 + ((long)c * p.NT + tile) * uH * TK, D, uH, ncol_valid, p.inv_norm, tid, T);
 }
 
 // k_row_c2r with a Bluestein transform of the rows.  grid (uH/2, 3); dynamic LDS = 2 * lpad_size(z.L) complex
@@ -158,18 +157,11 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_c2r_bz
     }
     __syncthreads();
     const float2* zz = fft_bluestein<-1, 1>(a, b, uW, z, tid, T);
-    const long plane = (long)uW * p.uH;
+    const long plane = (long)uW * p.uH, row = c * plane + (long)(2 * j) * uW;
     for (int n = tid; n < uW; n += T) {
         const float2 v = cscale(zz[lpad(n)], p.inv_norm);
-        if constexpr (HALF_OUT) {
-            __half* R = (__half*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = __float2half_rn(v.x);
-            R[uW + n] = __float2half_rn(v.y);
-        } else {
-            float* R = (float*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = v.x;
-            R[uW + n] = v.y;
-        }
+        store_px<HALF_OUT>(p.R, row, n, v.x);
+        store_px<HALF_OUT>(p.R, row, uW + n, v.y);
     }
 }
 

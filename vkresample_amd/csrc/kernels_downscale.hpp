@@ -93,12 +93,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_crop(D
     const int tile = blockIdx.x, c = blockIdx.y;
     const int H = p.H, uH = p.uH, hh = p.uH / 2;
     const int ncol_valid = min(TK, p.ncols - tile * TK);
-    const float2* src = p.S1 + ((long)c * p.NT + tile) * H * TK;
-    for (int e = tid; e < H * TK; e += T) {
-        float2 v = make_float2(0.f, 0.f);
-        if ((e % TK) < ncol_valid) v = src[e];
-        a[lpad(e)] = v;
-    }
+    load_col_tile<TK>(a, p.S1 + ((long)c * p.NT + tile) * H * TK, H, ncol_valid, tid, T);
     __syncthreads();
     float2* F;
     if constexpr (BZ) F = fft_any<+1, TK>(a, b, p.planH, p.twH, p.bzH, tid, T);
@@ -117,9 +112,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_crop(D
     const float2* D;
     if constexpr (BZ) D = fft_any<-1, TK>(G, F, p.planUH, p.twUH, p.bzUH, tid, T);
     else D = fft_lds<-1, TK>(G, F, p.planUH, p.twUH, tid, T);
-    float2* dst = p.S2 + ((long)c * p.NT + tile) * uH * TK;
-    for (int e = tid; e < uH * TK; e += T)
-        if ((e % TK) < ncol_valid) dst[e] = cscale(D[lpad(e)], p.inv_norm);
+    store_col_tile<TK>(p.S2 + ((long)c * p.NT + tile) * uH * TK, D, uH, ncol_valid, p.inv_norm, tid, T);
 }
 
 }  // namespace fftup

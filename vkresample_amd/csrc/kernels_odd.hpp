@@ -1,4 +1,12 @@
-// kernels_odd.hpp -- FFTUP_FLAG_ODD_SIZE (include/fftup.h): plans with an odd width or height, input or output.
+// kernels_odd.hpp -- the resampling kernels.  Written for FFTUP_FLAG_ODD_SIZE (include/fftup.h): plans with an odd width or height,
+// input or output; the rule below covers every parity and direction, so these kernels also run
+//   * the plans of fftup_plan_create_size (either direction per axis, centre alignment: the phase tables);
+//   * the forward rows of a size-generic FFTUP_FLAG_ANY_SIZE plan whose width needs a Bluestein transform: k_row_r2c_odd with
+//     kmax = W/2 and no fold is the size-generic unpack (its columns and inverse rows keep the reference's shift, read guard and
+//     doubled Nyquist bin: k_col_bz / k_row_c2r_bz, kernels_bluestein.hpp);
+//   * the forward rows of fftup_plan_create_view (kernels_view.hpp).
+// FFT downscale plans with four even lengths keep kernels of their own (kernels_downscale.hpp: the same rule with uW < W, uH < H written
+// out): on these kernels their 4096x2048 -> 2048x1024 frame measured 1.7 to 2.7 % slower, profiles/resample_kernels_ab.json.
 //
 // Such a plan computes exact trigonometric resampling per axis (scipy.signal.resample's rule), separably.  Per axis, for an input
 // of N points with spectrum X = DFT_N(x), an output of M points and K = min(N, M):
@@ -111,12 +119,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_odd(Od
     const int tile = blockIdx.x, c = blockIdx.y;
     const int H = p.H, uH = p.uH, K = min(H, uH);
     const int ncol_valid = min(TK, p.ncols - tile * TK);
-    const float2* src = p.S1 + ((long)c * p.NT + tile) * H * TK;
-    for (int e = tid; e < H * TK; e += T) {
-        float2 v = make_float2(0.f, 0.f);
-        if ((e % TK) < ncol_valid) v = src[e];
-        a[lpad(e)] = v;
-    }
+    load_col_tile<TK>(a, p.S1 + ((long)c * p.NT + tile) * H * TK, H, ncol_valid, tid, T);
     __syncthreads();
     float2* F = fft_any<+1, TK>(a, b, p.planH, p.twH, p.bzH, tid, T);
     float2* G = (F == a) ? b : a;
@@ -146,9 +149,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_odd(Od
     }
     __syncthreads();
     const float2* D = fft_any<-1, TK>(G, F, p.planUH, p.twUH, p.bzUH, tid, T);
-    float2* dst = p.S2 + ((long)c * p.NT + tile) * uH * TK;
-    for (int e = tid; e < uH * TK; e += T)
-        if ((e % TK) < ncol_valid) dst[e] = cscale(D[lpad(e)], p.inv_norm);
+    store_col_tile<TK>(p.S2 + ((long)c * p.NT + tile) * uH * TK, D, uH, ncol_valid, p.inv_norm, tid, T);
 }
 
 struct OddC2RParams {
@@ -209,19 +210,11 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_c2r_od
     }
     __syncthreads();
     const float2* zz = fft_any<-1, 1>(a, b, p.plan, p.tw, p.bz, tid, T);
-    const long plane = (long)uW * p.uH;
-    // (one element per store: with an odd uW the second row of a pair is not 4-byte aligned as binary16)
+    const long plane = (long)uW * p.uH, row = c * plane + (long)(2 * j) * uW;
     for (int n = tid; n < uW; n += T) {
         const float2 v = cscale(zz[lpad(n)], p.inv_norm);
-        if constexpr (HALF_OUT) {
-            __half* R = (__half*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = __float2half_rn(v.x);
-            if (two) R[uW + n] = __float2half_rn(v.y);
-        } else {
-            float* R = (float*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = v.x;
-            if (two) R[uW + n] = v.y;
-        }
+        store_px<HALF_OUT>(p.R, row, n, v.x);
+        if (two) store_px<HALF_OUT>(p.R, row, uW + n, v.y);
     }
 }
 

@@ -85,12 +85,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_view(V
     const int tile = blockIdx.x, c = blockIdx.y;
     const int H = p.H, uH = p.uH;
     const int ncol_valid = min(TK, p.ncols - tile * TK);
-    const float2* src = p.S1 + ((long)c * p.NT + tile) * H * TK;
-    for (int e = tid; e < H * TK; e += T) {
-        float2 v = make_float2(0.f, 0.f);
-        if ((e % TK) < ncol_valid) v = src[e];
-        a[lpad(e)] = v;
-    }
+    load_col_tile<TK>(a, p.S1 + ((long)c * p.NT + tile) * H * TK, H, ncol_valid, tid, T);
     __syncthreads();
     float2* F = fft_any<+1, TK>(a, b, p.planH, p.twH, p.bzH, tid, T);
     float2* G = (F == a) ? b : a;
@@ -103,9 +98,7 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_col_view(V
     }
     __syncthreads();
     const float2* D = fft_czt<TK>(G, F, p.z, tid, T);
-    float2* dst = p.S2 + ((long)c * p.NT + tile) * uH * TK;
-    for (int e = tid; e < uH * TK; e += T)
-        if ((e % TK) < ncol_valid) dst[e] = D[lpad(e)];
+    store_col_tile<TK>(p.S2 + ((long)c * p.NT + tile) * uH * TK, D, uH, ncol_valid, tid, T);
 }
 
 struct ViewC2RParams {
@@ -142,19 +135,11 @@ __global__ void __launch_bounds__(GenericMaxThreads<float2>::value) k_row_view_c
     }
     __syncthreads();
     const float2* zz = fft_czt<1>(a, b, p.z, tid, T);
-    const long plane = (long)uW * p.uH;
-    // (one element per store: with an odd uW the second row of a pair is not 4-byte aligned as binary16)
+    const long plane = (long)uW * p.uH, row = c * plane + (long)(2 * j) * uW;
     for (int n = tid; n < uW; n += T) {
         const float2 v = zz[lpad(n)];
-        if constexpr (HALF_OUT) {
-            __half* R = (__half*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = __float2half_rn(v.x);
-            if (two) R[uW + n] = __float2half_rn(v.y);
-        } else {
-            float* R = (float*)p.R + c * plane + (long)(2 * j) * uW;
-            R[n] = v.x;
-            if (two) R[uW + n] = v.y;
-        }
+        store_px<HALF_OUT>(p.R, row, n, v.x);
+        if (two) store_px<HALF_OUT>(p.R, row, uW + n, v.y);
     }
 }
 
