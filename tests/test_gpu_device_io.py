@@ -60,6 +60,7 @@ def _close_plans():
         up.close()
     _plans.clear()
     _host_cache.clear()
+    _fresh_cache.clear()
 
 
 def _plan(key):
@@ -343,6 +344,120 @@ def test_slots_untouched():
     assert np.array_equal(up.download_planar(0), planes) and up.output_checksum(0) == word_sum
     up.execute(1)                                          # ... and the input slot still holds f0
     assert np.array_equal(up.download_planar(0), planes) and up.output_checksum(0) == word_sum
+
+
+# ---------------------------------------------------------------- 8. what the last frame left behind: its lane, its tap
+# 512x256 -> 1024x512 is the smallest plan with ahead-of-time fused kernels; the default three streams.  The yardstick is a fresh
+# ring = 1 plan: upload -> execute(1) -> downloads, byte for byte.
+FS_W, FS_H = 512, 256
+SEED_A, SEED_B, SEED_C = 61, 62, 63
+_fresh_cache = {}
+
+
+def _fs_plan(precision, flags=0, ring=2):
+    import vkresample_amd as v
+    return v.Upscaler(FS_W, FS_H, 2.0, precision, flags=flags, ring=ring)
+
+
+def _fs_frame(seed):
+    from vkresample_amd import synth
+    return synth.frame(seed, FS_W, FS_H, "N")
+
+
+def _fresh(precision, flags, seed, planar=False):
+    """{"out", "tap", "rgb8"} of one frame on a fresh ring = 1 plan after execute(1); computed once, shared and left unchanged.
+    The fresh plan carries FFTUP_FLAG_OVERLAP_ITERATIONS: the strip length of the fused C2R+sharpen kernel is a property of the
+    plan, chosen by whether its frames overlap (strip_length, plan_rules.cpp), and fp32 outputs depend on the cuts in their last
+    bits (test_fused_output_independent_of_strip_length) -- without the flag a ring = 1 plan cuts a frame differently from the
+    ring = 2 plan under test and their fp32 outputs differ (taps, binary16 and unfused outputs do not).  One iteration runs on
+    lane 0 with or without it."""
+    import vkresample_amd as v
+    k = (precision, flags, seed, planar)
+    if k not in _fresh_cache:
+        with _fs_plan(precision, flags | v.FLAG_OVERLAP_ITERATIONS, ring=1) as up:
+            if planar:
+                up.upload_planar(_frame(up, PLANAR, seed))
+            else:
+                up.upload_rgb8(_fs_frame(seed))
+            up.execute(1)
+            res = {"out": up.download_planar(), "tap": up.download_presharpen(), "rgb8": up.download_rgb8()}
+        for a in res.values():
+            a.flags.writeable = False
+        _fresh_cache[k] = res
+    return _fresh_cache[k]
+
+
+def _ring_run_ab(up):
+    """A in slot 0, B in slot 1, two frames: with more than one stream the run ends on lane 1"""
+    up.upload_rgb8(_fs_frame(SEED_A), slot=0)
+    up.upload_rgb8(_fs_frame(SEED_B), slot=1)
+    up.execute_ring(2)
+
+
+def _unfused():
+    import vkresample_amd as v
+    return v.FLAG_UNFUSED_SHARPEN
+
+
+FS_CASES = [(0, False), (2, False), (0, True), (2, True)]
+FS_IDS = ["p0", "p2", "p0_unfused", "p2_unfused"]
+
+
+@pytest.mark.parametrize("precision,unfused", FS_CASES, ids=FS_IDS)
+def test_tap_after_a_ring_run_that_ends_on_lane_1(precision, unfused):
+    """fused plans: the tap is rebuilt from lane 1's spectra; unfused ones: it is lane 1's own pre-sharpen image"""
+    flags = _unfused() if unfused else 0
+    a, b = _fresh(precision, flags, SEED_A), _fresh(precision, flags, SEED_B)
+    assert not np.array_equal(a["tap"], b["tap"])
+    with _fs_plan(precision, flags) as up:
+        _ring_run_ab(up)
+        assert np.array_equal(up.download_planar(0), a["out"])
+        assert np.array_equal(up.download_planar(1), b["out"])
+        assert np.array_equal(up.download_presharpen(), b["tap"])
+
+
+@pytest.mark.parametrize("precision", [0, 2], ids=["p0", "p2"])
+def test_tap_after_the_queue_ends_on_lane_1(precision):
+    a, b = _fresh(precision, 0, SEED_A), _fresh(precision, 0, SEED_B)
+    with _fs_plan(precision) as up:
+        ins = np.stack([_fs_frame(SEED_A), _fs_frame(SEED_B)])
+        outs = np.zeros((2, 2 * FS_H, 2 * FS_W, 3), np.uint8)
+        for k in range(2):
+            up.submit_rgb8(ins[k], outs[k])
+        up.drain()
+        assert np.array_equal(outs[0], a["rgb8"]) and np.array_equal(outs[1], b["rgb8"])
+        assert np.array_equal(up.download_presharpen(), b["tap"])
+
+
+@pytest.mark.parametrize("precision,unfused", FS_CASES, ids=FS_IDS)
+def test_tap_follows_profile_kernels(precision, unfused):
+    """profile_kernels(1) runs slot 0 (frame A) on lane 0 after a ring run that ended on lane 1 with frame B: the tap belongs to
+    the frame that ran last, A.  (Before the frame context, fftup_profile_kernels left the tap's lane as the ring run had set it,
+    and the tap returned B's: assertion failure on every one of the four cases.)"""
+    flags = _unfused() if unfused else 0
+    a, b = _fresh(precision, flags, SEED_A), _fresh(precision, flags, SEED_B)
+    with _fs_plan(precision, flags) as up:
+        _ring_run_ab(up)
+        assert np.array_equal(up.download_presharpen(), b["tap"])
+        up.profile_kernels(1)
+        assert np.array_equal(up.download_presharpen(), a["tap"])
+
+
+@pytest.mark.parametrize("precision", [0, 2], ids=["p0", "p2"])
+def test_ring_run_device_frame_ring_run_leave_nothing_behind(precision):
+    """ring run, a device frame C (planes one byte off alignment: staged; padded 8-bit output: lane scratch + strided pack), the
+    same ring run again: the second run's slots and checksums equal the first's, and C equals C through the host path"""
+    c = _fresh(precision, 0, SEED_C, planar=True)
+    with _fs_plan(precision) as up:
+        _ring_run_ab(up)
+        first = [(up.download_planar(s), up.output_checksum(s)) for s in range(2)]
+        got, clean = _device_run(up, PLANAR, _frame(up, PLANAR, SEED_C), RGB8, out_padded=True, in_base=GUARD + 1)
+        assert np.array_equal(got, c["rgb8"].reshape(-1)) and clean
+        up.execute_ring(2)
+        for s in range(2):
+            assert np.array_equal(up.download_planar(s), first[s][0]) and up.output_checksum(s) == first[s][1]
+        assert np.array_equal(first[0][0], _fresh(precision, 0, SEED_A)["out"])
+        assert np.array_equal(first[1][0], _fresh(precision, 0, SEED_B)["out"])
 
 
 if __name__ == "__main__":

@@ -81,8 +81,6 @@ int ensure_events(fftup_plan* P)
 {
     if (P->dio.start) return FFTUP_OK;
     HIP_TRY(hipEventCreateWithFlags(&P->dio.start, hipEventDisableTiming));
-    P->dio.done.assign(P->nlanes, nullptr);
-    for (auto& e : P->dio.done) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
     P->dio.stage_in.assign(P->nlanes, nullptr);
     P->dio.scratch_out.assign(P->nlanes, nullptr);
     return FFTUP_OK;
@@ -115,14 +113,13 @@ int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftu
         if (!route_out(P, out[i]).in_place && !P->dio.scratch_out[l] && (rc = dev_alloc(P, &P->dio.scratch_out[l], out_bytes + 8))) return rc;
     }
     hipStream_t cs = (hipStream_t)stream;
-    HIP_TRY(hipEventRecord(P->dio.start, cs));
-    for (int l = 0; l < nl; l++) HIP_TRY(hipStreamWaitEvent(P->lanes[l].stream, P->dio.start, 0));
+    if ((rc = lanes_fork(P, P->dio.start, cs, 0, nl))) return rc;
     for (uint32_t i = 0; i < n_frames && !rc; i++) {
         const int l = (int)(i % (uint32_t)nl);
         hipStream_t st = P->lanes[l].stream;
         const fftup_device_image &src = in[i], &dst = out[i];
         const Route ri = route_in(P, src), ro = route_out(P, dst);
-        fftup_plan::FrameIO io;
+        DeviceInput io;
         if (src.format == FFTUP_FMT_RGB8 && ri.in_place) {    // FFTUP_FLAG_FUSE_U8_LOAD: the row kernel reads the caller's bytes
             io.in = src.data; io.kind = 2; io.in_row = (long)src.row_stride_bytes;
         } else if (ri.in_place) {
@@ -134,32 +131,22 @@ int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftu
                                   P->W * esz, P->H, 3, 1, st);             // (the source is not element aligned: bytes)
             io.in = stage; io.kind = 1; io.in_row = (long)P->W; io.in_plane = (long)P->in_plane_stride;
         }
-        io.out = ro.in_place ? dst.data : P->dio.scratch_out[l];
-        P->cur = l;
-        P->io = &io;
-        rc = launch_frame(P, 0, 0, -1);
-        P->io = nullptr;
-        P->cur = 0;
-        P->last_lane = l;
-        if (rc) break;
+        const FrameRun r{l, 0, ro.in_place ? dst.data : P->dio.scratch_out[l], &io};
+        if ((rc = launch_frame(P, r))) break;
         if (!ro.in_place) {
             if (dst.format == FFTUP_FMT_PLANAR)
-                launch_copy_rows(io.out, P->uW * esz, (size_t)P->uW * P->uH * esz, dst.data, dst.row_stride_bytes, dst.plane_stride_bytes,
+                launch_copy_rows(r.out, P->uW * esz, (size_t)P->uW * P->uH * esz, dst.data, dst.row_stride_bytes, dst.plane_stride_bytes,
                                  P->uW * esz, P->uH, 3, ro.gran, st);
             else if (P->u8out)
-                launch_copy_rows(io.out, (size_t)3 * P->uW, 0, dst.data, dst.row_stride_bytes, 0, (size_t)3 * P->uW, P->uH, 1, 1, st);
-            else launch_pack_to(P, io.out, (uint8_t*)dst.data, dst.row_stride_bytes, st);
+                launch_copy_rows(r.out, (size_t)3 * P->uW, 0, dst.data, dst.row_stride_bytes, 0, (size_t)3 * P->uW, P->uH, 1, 1, st);
+            else launch_pack_to(P, r.out, (uint8_t*)dst.data, dst.row_stride_bytes, st);
         }
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) rc = fail(FFTUP_E_HIP, std::string("kernel launch: ") + hipGetErrorString(e));
     }
     // `stream` goes on behind every lane used; so does the plan's own stream, on which the taps and every other entry point run
-    for (int l = 0; l < nl; l++) {
-        const hipError_t e1 = hipEventRecord(P->dio.done[l], P->lanes[l].stream);
-        const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(cs, P->dio.done[l], 0) : e1;
-        const hipError_t e3 = (e2 == hipSuccess && l > 0) ? hipStreamWaitEvent(P->stream, P->dio.done[l], 0) : e2;
-        if (!rc && e3 != hipSuccess) rc = fail(FFTUP_E_HIP, std::string("event: ") + hipGetErrorString(e3));
-    }
+    // (lane 0 runs on the plan's own stream)
+    rc = lanes_join(P, 0, nl, {cs, P->stream}, rc);
     if (!rc) P->dev_executed = true;
     return rc;
 }

@@ -58,6 +58,24 @@ int fftup_upload_planar(fftup_plan* P, uint32_t slot, const void* planes, size_t
 
 }  // extern "C"
 
+int lanes_fork(fftup_plan* P, hipEvent_t ev, hipStream_t from, int first, int nl)
+{
+    HIP_TRY(hipEventRecord(ev, from));
+    for (int l = first; l < nl; l++) HIP_TRY(hipStreamWaitEvent(P->lanes[l].stream, ev, 0));
+    return FFTUP_OK;
+}
+int lanes_join(fftup_plan* P, int first, int nl, std::initializer_list<hipStream_t> into, int rc)
+{
+    for (int l = first; l < nl; l++) {
+        const fftup_plan::Lane& lane = P->lanes[l];
+        hipError_t e = hipEventRecord(lane.done, lane.stream);
+        for (hipStream_t s : into)
+            if (e == hipSuccess && s != lane.stream) e = hipStreamWaitEvent(s, lane.done, 0);
+        if (!rc && e != hipSuccess) rc = fail(FFTUP_E_HIP, std::string("lane join: ") + hipGetErrorString(e));
+    }
+    return rc;
+}
+
 // shared body of fftup_execute_ring / fftup_execute_ring_timed (and of the plan-time tuner's timing, fftup_plan.hip).  With kernel_ms != NULL a HIP event is recorded
 // before and after every kernel launch ON THE STREAM THAT RUNS IT (one event chain per lane) and the average
 // duration of each of the plan's kernels over this very batch is returned.
@@ -78,29 +96,24 @@ int execute_ring_impl(fftup_plan* P, uint32_t n_frames, uint32_t first_slot, dou
     }
     // consecutive frames go to distinct lanes; they must then also write distinct output slots
     const int nl = std::max(1, std::min(P->nlanes, (int)P->ring));
-    HIP_TRY(hipEventRecord(P->ev0, P->stream));
-    for (int l = 1; l < nl; l++) HIP_TRY(hipStreamWaitEvent(P->lanes[l].stream, P->ev0, 0));
-    int rc = FFTUP_OK;
+    int rc = lanes_fork(P, P->ev0, P->stream, 1, nl);
+    if (rc) return rc;
     for (uint32_t i = 0; i < n_frames && !rc; i++) {
-        uint32_t s = (first_slot + i) % P->ring;
-        P->cur = (int)(i % (uint32_t)nl);
+        const uint32_t s = (first_slot + i) % P->ring;
+        FrameRun r{(int)(i % (uint32_t)nl), s, P->out[s]};
         if (kernel_ms && i % stride == 0) {
             hipEvent_t* e = &ev[(size_t)(i / stride) * (nk + 1)];
-            (void)hipEventRecord(e[0], P->lanes[P->cur].stream);
+            (void)hipEventRecord(e[0], P->lanes[r.lane].stream);
             for (int k = 0; k < nk && !rc; k++) {
-                rc = launch_frame(P, s, s, k);
-                (void)hipEventRecord(e[k + 1], P->lanes[P->cur].stream);
+                r.pass = (Pass)k;
+                rc = launch_frame(P, r);
+                (void)hipEventRecord(e[k + 1], P->lanes[r.lane].stream);
             }
         } else {
-            rc = launch_frame(P, s, s, -1);
+            rc = launch_frame(P, r);
         }
-        P->last_lane = P->cur;
-        P->cur = 0;
     }
-    for (int l = 1; l < nl; l++) {
-        (void)hipEventRecord(P->lanes[l].done, P->lanes[l].stream);
-        (void)hipStreamWaitEvent(P->stream, P->lanes[l].done, 0);
-    }
+    rc = lanes_join(P, 1, nl, {P->stream}, rc);
     hipError_t e1 = hipEventRecord(P->ev1, P->stream);
     hipError_t e2 = hipEventSynchronize(P->ev1);
     if (!rc && (e1 != hipSuccess || e2 != hipSuccess)) rc = fail(FFTUP_E_HIP, std::string("sync: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
@@ -166,18 +179,13 @@ int fftup_execute(fftup_plan* P, uint32_t n_iter, double* ms_per_iter)
     const int nl = sequential ? 1 : (int)std::min<uint32_t>((uint32_t)P->nlanes, n_iter);
     int rc = ensure_execute_outputs(P, nl);
     if (rc) return rc;
-    P->last_lane = 0;
-    HIP_TRY(hipEventRecord(P->ev0, P->stream));
-    for (int l = 1; l < nl; l++) HIP_TRY(hipStreamWaitEvent(P->lanes[l].stream, P->ev0, 0));
+    if ((rc = lanes_fork(P, P->ev0, P->stream, 1, nl))) return rc;
     for (uint32_t i = 0; i < n_iter && !rc; i++) {
-        P->cur = (int)(i % (uint32_t)nl);
-        rc = launch_frame(P, 0, P->cur == 0 ? 0 : P->ring + (uint32_t)P->cur - 1, -1);
+        const uint32_t l = i % (uint32_t)nl;
+        rc = launch_frame(P, {(int)l, 0, P->out[l == 0 ? 0 : P->ring + l - 1]});
     }
-    P->cur = 0;
-    for (int l = 1; l < nl; l++) {
-        (void)hipEventRecord(P->lanes[l].done, P->lanes[l].stream);
-        (void)hipStreamWaitEvent(P->stream, P->lanes[l].done, 0);
-    }
+    P->last_lane = 0;          // the one writer besides launch_frame: every iteration computed the same frame, and the tap reads lane 0's, like the downloads
+    rc = lanes_join(P, 1, nl, {P->stream}, rc);
     const hipError_t e1 = hipEventRecord(P->ev1, P->stream), e2 = hipEventSynchronize(P->ev1);
     if (rc) return rc;
     if (e1 != hipSuccess || e2 != hipSuccess) return fail(FFTUP_E_HIP, std::string("sync: ") + hipGetErrorString(e1 != hipSuccess ? e1 : e2));
@@ -215,7 +223,7 @@ int fftup_profile_kernels(fftup_plan* P, uint32_t n_iter, double* ms_per_kernel)
         (void)hipEventRecord(e[0], P->stream);
         for (int k = 0; k < FFTUP_NUM_KERNELS && !rc; k++) {
             if (evict) (void)hipMemsetAsync(evict, (int)(i + k) & 255, evict_bytes, P->stream);
-            rc = launch_frame(P, i % P->ring, i % P->ring, k);
+            rc = launch_frame(P, {0, i % P->ring, P->out[i % P->ring], nullptr, (Pass)k});
             (void)hipEventRecord(e[k + 1], P->stream);
         }
         (void)hipEventRecord(e[FFTUP_NUM_KERNELS + 1], P->stream);
@@ -268,11 +276,8 @@ int fftup_download_presharpen(fftup_plan* P, void* planes)
         if (!P->lanes[P->last_lane].R) {
             int rc = dev_alloc(P, &P->lanes[P->last_lane].R, P->r_bytes);
             if (rc) return rc;
-            if (P->last_lane == 0) P->R = P->lanes[0].R;
         }
-        P->cur = P->last_lane;
-        const int rc = launch_frame(P, 0, 0, 22);
-        P->cur = 0;
+        const int rc = launch_frame(P, {P->last_lane, 0, nullptr, nullptr, Pass::presharpen_tap});
         if (rc) return rc;
         HIP_TRY(hipStreamSynchronize(P->lanes[P->last_lane].stream));
     }

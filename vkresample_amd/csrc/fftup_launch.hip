@@ -1,11 +1,12 @@
 // fftup_launch.hip -- the frame's kernel launches: the ONLY translation unit that instantiates the frame kernels (kernels_*.hpp).
-// One frame = row R2C -> column FFT / zero-pad / iFFT -> row C2R + sharpen (fused) on the stream of lane P->cur; the
+// One frame = row R2C -> column FFT / zero-pad / iFFT -> row C2R + sharpen (fused) on the stream of the lane its caller names; the
 // reference's 20 dispatches per frame (performVulkanUpscale, VkResample.cpp:1249-1279).
 // Layout: (1) the kernel selectors -- per pass and plan family ONE function from the plan's fields (and the input kind) to the
 // kernel instantiation with its block size and dynamic LDS bytes; (2) kernels_set_attributes, which asks the selectors for
-// every kernel the plan can launch and allows it those bytes; (3) the frame functions per family, which ask the same selectors,
-// compute grid and parameters per launch and launch; (4) launch_frame, a switch on P->family.  A kernel instantiation is
-// spelled in its selector and nowhere else.
+// every kernel the plan can launch and allows it those bytes; (3) the frame functions per family, functions of (const plan,
+// Frame, Pass), which ask the same selectors, compute grid and parameters per launch and launch; (4) launch_frame, which
+// resolves its caller's FrameRun into the Frame, switches on P->family, and alone records what the frame left in the plan
+// (last_lane, R_valid).  A kernel instantiation is spelled in its selector and nowhere else.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -42,21 +43,23 @@ int kernels_aot_mixed_plan(uint32_t W, uint32_t H)
 }
 size_t kernels_tuned_col_lds(uint32_t H) { return sizeof(float2) * (size_t)lswz_size((int)H * TUNED_TK); }   // both transforms of the column kernel have length H
 
-// where the frame being launched reads and writes: the ring slots, or what fftup_execute_device names (P->io: caller memory or
-// the lane's staging, with the caller's strides)
-static int frame_kind(const fftup_plan* P, uint32_t slot) { return P->io ? P->io->kind : P->in_kind[slot]; }
-static void* frame_out(const fftup_plan* P, uint32_t slot) { return P->io ? P->io->out : P->out[slot]; }
-// the input of a forward row kernel: 8-bit RGB (kind 2) or planes
-template <class Q> static void set_in(const fftup_plan* P, uint32_t slot, int kind, Q& q)
+// One frame as the frame functions see it, a FrameRun resolved once by launch_frame: the lane's stream and buffers, where the first kernel
+// reads (a ring slot or the caller's DeviceInput; kind 1 planes, 2 8-bit RGB, 0 nothing uploaded) and where the last one writes
+struct Frame { hipStream_t st; float2 *S1, *S2; void *R, *T4; const void* in; long in_row, in_plane; int kind; void* out; };
+static Frame resolve(const fftup_plan* P, const FrameRun& r)
 {
-    if (P->io) { q.in = P->io->in; q.in_row_stride = P->io->in_row; q.in_plane_stride = kind == 2 ? 0 : P->io->in_plane; }
-    else if (kind == 2) { q.in = P->in_u8[slot]; q.in_row_stride = 3l * P->W; q.in_plane_stride = 0; }
-    else { q.in = P->in_planar[slot]; q.in_row_stride = P->W; q.in_plane_stride = (long)P->in_plane_stride; }
+    const fftup_plan::Lane& l = P->lanes[r.lane];
+    Frame f{l.stream, l.S1, l.S2, l.R, l.T4, P->in_planar[r.in_slot], (long)P->W, (long)P->in_plane_stride, P->in_kind[r.in_slot], r.out};
+    if (r.in) { f.in = r.in->in; f.in_row = r.in->in_row; f.in_plane = r.in->kind == 2 ? 0 : r.in->in_plane; f.kind = r.in->kind; }
+    else if (f.kind == 2) { f.in = P->in_u8[r.in_slot]; f.in_row = 3l * P->W; f.in_plane = 0; }
+    return f;
 }
+template <class Q> static void set_in(const Frame& f, Q& q) { q.in = f.in; q.in_row_stride = f.in_row; q.in_plane_stride = f.in_plane; }   // a forward row kernel's input
+static bool runs(Pass pass, Pass k) { return pass == Pass::all || pass == k; }
 
 // ------------------------------------------------------------------------------------------------
 // A kernel as a selector hands it out: what may be resolved ahead of a launch (grids and parameters are the launch's business:
-// fftup_plan_set_view changes NT / ncols / kmax on a live plan, P->io, P->cur and the slots change per frame)
+// fftup_plan_set_view changes NT / ncols / kmax on a live plan, lane and images change per frame)
 template <class... A> struct Kern { void (*fn)(A...); unsigned block; size_t lds; };
 template <class... A> static Kern<A...> kern(void (*fn)(A...), int block, size_t lds) { return {fn, (unsigned)block, lds}; }
 template <class T> struct type_c { using type = T; };
@@ -388,12 +391,12 @@ static unsigned fused_grid(const fftup_plan* P, int pairs_per_strip)
     if (P->u8out) return (unsigned)(((ppp + pairs_per_strip - 1) / pairs_per_strip + 7) / 8 * 24);
     return (unsigned)((3 * ppp + pairs_per_strip - 1) / pairs_per_strip);
 }
-static FusedParams fused_params(fftup_plan* P, uint32_t out_slot)
+static FusedParams fused_params(const fftup_plan* P, const Frame& f)
 {
     FusedParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.odd_delta = (unsigned)(P->lanes[P->cur].S2 - P->lanes[P->cur].S1);
-    if (P->U == 1) { p.S1 = P->lanes[P->cur].S2; p.odd_delta = 0; }      // half-integer factor: one buffer with all rows (k_col_pad)
-    p.out = frame_out(P, out_slot); p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
+    p.S1 = f.S1; p.odd_delta = (unsigned)(f.S2 - f.S1);
+    if (P->U == 1) { p.S1 = f.S2; p.odd_delta = 0; }      // half-integer factor: one buffer with all rows (k_col_pad)
+    p.out = f.out; p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
     p.pairs_per_strip = P->pairs_per_strip; p.upsq = P->upsq; p.coef = P->coef;
     p.u8_wrap = (P->cfg.flags & FFTUP_FLAG_U8_WRAP) ? 1 : 0;
     return p;
@@ -401,24 +404,24 @@ static FusedParams fused_params(fftup_plan* P, uint32_t out_slot)
 
 static bool fast_sharpen_ok(const fftup_plan* P) { return !P->dbl && P->uW % 256 == 0 && P->uH % 16 == 0; }
 
-static void launch_sharpen_fast(fftup_plan* P, uint32_t out_slot)
+static void launch_sharpen_fast(const fftup_plan* P, const Frame& f)
 {
     SharpenTParams p{};
-    p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
     dim3 grid(P->uW / 256, P->uH / 16, 3), block(64, 4);
-    if (P->half) hipLaunchKernelGGL((k_sharpen_t<true, 4>), grid, block, 0, P->lanes[P->cur].stream, p);
-    else hipLaunchKernelGGL((k_sharpen_t<false, 4>), grid, block, 0, P->lanes[P->cur].stream, p);
+    if (P->half) hipLaunchKernelGGL((k_sharpen_t<true, 4>), grid, block, 0, f.st, p);
+    else hipLaunchKernelGGL((k_sharpen_t<false, 4>), grid, block, 0, f.st, p);
 }
 
-// the sharpen pass of an unfused fp32 / fp16 plan on lane P->cur: R -> output slot
-static void launch_sharpen(fftup_plan* P, uint32_t out_slot)
+// the sharpen pass of an unfused fp32 / fp16 plan: R -> the frame's output image
+static void launch_sharpen(const fftup_plan* P, const Frame& f)
 {
-    if (fast_sharpen_ok(P)) { launch_sharpen_fast(P, out_slot); return; }
+    if (fast_sharpen_ok(P)) { launch_sharpen_fast(P, f); return; }
     SharpenParams p{};
-    p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
     dim3 grid((P->uW + 1023) / 1024, P->uH, 3), block(256);      // (four pixels per thread; a width of 2 gave an empty grid until round 5)
-    if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, P->lanes[P->cur].stream, p);
-    else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, P->lanes[P->cur].stream, p);
+    if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, f.st, p);
+    else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, f.st, p);
 }
 
 // the end of every frame function: the first failing launch of the frame wins (`jit`: launches from a run-time specialised code
@@ -433,67 +436,66 @@ static int frame_status(hipError_t jit = hipSuccess)
 
 // The frame of the families with four launches on fp32 / fp16 data: forward rows, columns, inverse rows into R, sharpen
 template <class Rows, class Cols, class Inv>
-static int launch_four_passes(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which, Rows rows, Cols cols, Inv inv)
+static int launch_four_passes(const fftup_plan* P, const Frame& f, Pass pass, Rows rows, Cols cols, Inv inv)
 {
-    hipStream_t st = P->lanes[P->cur].stream;
-    if (which < 0 || which == 0) rows(P, in_slot, frame_kind(P, in_slot), st);
-    if (which < 0 || which == 1) cols(P, st);
-    if (which < 0 || which == 2) { inv(P, st); P->R_valid = true; }
-    if (which < 0 || which == 3) launch_sharpen(P, out_slot);
+    if (runs(pass, Pass::rows)) rows(P, f);
+    if (runs(pass, Pass::columns)) cols(P, f);
+    if (runs(pass, Pass::inverse)) inv(P, f);
+    if (runs(pass, Pass::sharpen)) launch_sharpen(P, f);
     return frame_status();
 }
 
 // ---- FFTUP_FLAG_DCT: DCT-II rows -> DCT-II columns, zero-pad, DCT-III columns -> DCT-III rows -> sharpen (kernels_dct.hpp)
-static void dct_rows(fftup_plan* P, uint32_t in_slot, int kind, hipStream_t st)
+static void dct_rows(const fftup_plan* P, const Frame& f)
 {
     DctRowParams p{};
-    p.S1 = (float*)P->lanes[P->cur].S1; p.tw = P->twW; p.rot = P->rotW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
-    set_in(P, in_slot, kind, p);
-    launch(dct_row_kernel(P, kind), dim3(P->H / 2, 3), st, p);
+    p.S1 = (float*)f.S1; p.tw = P->twW; p.rot = P->rotW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+    set_in(f, p);
+    launch(dct_row_kernel(P, f.kind), dim3(P->H / 2, 3), f.st, p);
 }
-static void dct_cols(fftup_plan* P, hipStream_t st)
+static void dct_cols(const fftup_plan* P, const Frame& f)
 {
     DctColParams p{};
-    p.S1 = (const float*)P->lanes[P->cur].S1; p.S2 = (float*)P->lanes[P->cur].S2;
+    p.S1 = (const float*)f.S1; p.S2 = (float*)f.S2;
     p.twH = P->twH; p.twUH = P->twUH; p.rotH = P->rotH; p.rotUH = P->rotUH; p.planH = P->planH; p.planUH = P->planUH;
     p.W = (int)P->W; p.H = (int)P->H; p.uH = (int)P->uH; p.inv_norm = (float)(1.0 / (double)P->H);
-    launch(dct_col_kernel(P), dim3((P->W / 2 + P->TK - 1) / P->TK, 3), st, p);
+    launch(dct_col_kernel(P), dim3((P->W / 2 + P->TK - 1) / P->TK, 3), f.st, p);
 }
-static void dct_inv(fftup_plan* P, hipStream_t st)
+static void dct_inv(const fftup_plan* P, const Frame& f)
 {
     IdctRowParams p{};
-    p.S2 = (const float*)P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.rot = P->rotUW; p.plan = P->planUW;
+    p.S2 = (const float*)f.S2; p.R = f.R; p.tw = P->twUW; p.rot = P->rotUW; p.plan = P->planUW;
     p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH;
     p.inv_norm = (float)(1.0 / ((double)P->W * (double)P->upsq));
-    launch(idct_row_kernel(P), dim3(P->uH / 2, 3), st, p);
+    launch(idct_row_kernel(P), dim3(P->uH / 2, 3), f.st, p);
 }
 
 // ---- FFTUP_FLAG_DOWNSCALE (FFT mode): row R2C keeping kx <= uW/2 -> column forward / crop / inverse -> the upscale path's C2R with
 // W := uW and no read guard -> sharpen (kernels_downscale.hpp)
-static void down_rows(fftup_plan* P, uint32_t in_slot, int kind, hipStream_t st)
+static void down_rows(const fftup_plan* P, const Frame& f)
 {
     DownRowParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+    p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
     p.TK = P->TK; p.NT = P->NT; p.h = (int)P->uW / 2; p.bz = P->bzW;
-    set_in(P, in_slot, kind, p);
-    launch(crop_row_kernel(P, kind), dim3(P->H / 2, 3), st, p);
+    set_in(f, p);
+    launch(crop_row_kernel(P, f.kind), dim3(P->H / 2, 3), f.st, p);
 }
-static void down_cols(fftup_plan* P, hipStream_t st)
+static void down_cols(const fftup_plan* P, const Frame& f)
 {
     DownColParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
+    p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
     p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
     p.bzH = P->bzH; p.bzUH = P->bzUH;
-    launch(crop_col_kernel(P), dim3(P->NT, 3), st, p);
+    launch(crop_col_kernel(P), dim3(P->NT, 3), f.st, p);
 }
-static void down_inv(fftup_plan* P, hipStream_t st)
+static void down_inv(const fftup_plan* P, const Frame& f)
 {
     // W := uW: every bin k <= uW/2 is read; the empty guard [0, 0); the folded Nyquist bin is real, so the kernel's two writes
     // of a[uW/2] (from k and from uW - k) store the same value
     RowC2RParams p{};
-    p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->uW; p.uW = (int)P->uW;
+    p.S2 = f.S2; p.R = f.R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->uW; p.uW = (int)P->uW;
     p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = 0; p.zrx = 0; p.inv_norm = 1.0f / (float)P->uW; p.poly = 0;
-    generic_c2r_kernel(P, [&](auto k, const auto&... z) { launch(k, dim3(P->uH / 2, 3), st, p, z...); });
+    generic_c2r_kernel(P, [&](auto k, const auto&... z) { launch(k, dim3(P->uH / 2, 3), f.st, p, z...); });
 }
 
 // ---- FFTUP_FLAG_ODD_SIZE with an odd length: row R2C keeping kx <= min(W, uW)/2 -> column forward / bin map / inverse -> row C2R ->
@@ -501,33 +503,33 @@ static void down_inv(fftup_plan* P, hipStream_t st)
 // Plans of fftup_plan_create_size run the same four launches, each axis with its own direction, centre-aligned ones with phase tables.
 // fftup_plan_create_view runs the same row R2C keeping kx <= kmax_x, without fold or phase table.  Size-generic plans with
 // Bluestein forward rows run it too: kmax = W/2 (uW >= W), no fold, P->phW == nullptr.
-static void odd_rows(fftup_plan* P, uint32_t in_slot, int kind, hipStream_t st)
+static void odd_rows(const fftup_plan* P, const Frame& f)
 {
     const bool view = P->family == Family::view;
     OddRowParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+    p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
     p.TK = P->TK; p.NT = P->NT; p.bz = P->bzW;
     p.kmax = view ? P->vx.kmax : (int)std::min(P->W, P->uW) / 2;
     p.fold = (!view && P->uW < P->W && !(P->uW & 1)) ? 1 : 0;
     p.ph = view ? nullptr : P->phW;
-    set_in(P, in_slot, kind, p);
-    launch(odd_row_kernel(P, kind), dim3((P->H + 1) / 2, 3), st, p);
+    set_in(f, p);
+    launch(odd_row_kernel(P, f.kind), dim3((P->H + 1) / 2, 3), f.st, p);
 }
-static void odd_cols(fftup_plan* P, hipStream_t st)
+static void odd_cols(const fftup_plan* P, const Frame& f)
 {
     OddColParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
+    p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.twUH = P->twUH; p.planH = P->planH; p.planUH = P->planUH;
     p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.inv_norm = 1.0f / (float)P->uH;
     p.bzH = P->bzH; p.bzUH = P->bzUH; p.ph = P->phH;
-    launch(odd_col_kernel(P), dim3(P->NT, 3), st, p);
+    launch(odd_col_kernel(P), dim3(P->NT, 3), f.st, p);
 }
-static void odd_inv(fftup_plan* P, hipStream_t st)
+static void odd_inv(const fftup_plan* P, const Frame& f)
 {
     OddC2RParams p{};
-    p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.uW = (int)P->uW; p.uH = (int)P->uH;
+    p.S2 = f.S2; p.R = f.R; p.tw = P->twUW; p.plan = P->planUW; p.uW = (int)P->uW; p.uH = (int)P->uH;
     p.TK = P->TK; p.NT = P->NT; p.kmax = (int)std::min(P->W, P->uW) / 2; p.halve = (P->uW > P->W && !(P->W & 1)) ? 1 : 0; p.inv_norm = 1.0f / (float)P->uW;
     p.bz = P->bzUW;
-    launch(odd_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), st, p);
+    launch(odd_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
 }
 
 // ---- fftup_plan_create_view: the odd-size plans' row R2C -> column forward / signed bins / chirp-z to uH points -> two spectrum
@@ -538,19 +540,19 @@ static CztPlan czt_plan(const fftup_plan::ViewAxis& a, uint32_t M)
     z.L = (int32_t)a.L; z.K = 2 * a.kmax + 1; z.M = (int32_t)M; z.plan = a.planL; z.tw = a.tw; z.pre = a.pre; z.post = a.post; z.bhat = a.bhat;
     return z;
 }
-static void view_cols(fftup_plan* P, hipStream_t st)
+static void view_cols(const fftup_plan* P, const Frame& f)
 {
     ViewColParams p{};
-    p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.planH = P->planH;
+    p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.planH = P->planH;
     p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.kmax = P->vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, P->uH);
-    launch(view_col_kernel(P), dim3(P->NT, 3), st, p);
+    launch(view_col_kernel(P), dim3(P->NT, 3), f.st, p);
 }
-static void view_inv(fftup_plan* P, hipStream_t st)
+static void view_inv(const fftup_plan* P, const Frame& f)
 {
     ViewC2RParams p{};
-    p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.uW = (int)P->uW; p.uH = (int)P->uH;
+    p.S2 = f.S2; p.R = f.R; p.uW = (int)P->uW; p.uH = (int)P->uH;
     p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.z = czt_plan(P->vx, P->uW);
-    launch(view_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), st, p);
+    launch(view_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
 }
 
 // ---- four-step transforms (k_row4_a / k_row4_b): both passes of one
@@ -561,225 +563,222 @@ template <typename C> static void launch_four(const FourKerns<C>& k, const fftup
 }
 // the column pass of the size-generic plans on C: in LDS, or -- columns longer than the LDS -- in four steps, forward in place
 // in S1 (tiles of one column = dense columns), inverse S1 -> S2 with shift and guard
-template <typename C> static void launch_columns(fftup_plan* P, hipStream_t st)
+template <typename C> static void launch_columns(const fftup_plan* P, const Frame& f)
 {
     using S = scalar_t<C>;
     if (!P->colF.on) {
         ColParamsT<C> p{};
-        p.S1 = (const C*)P->lanes[P->cur].S1; p.S2 = (C*)P->lanes[P->cur].S2; p.twH = (const C*)P->twH; p.twUH = (const C*)P->twUH;
+        p.S1 = (const C*)f.S1; p.S2 = (C*)f.S2; p.twH = (const C*)P->twH; p.twUH = (const C*)P->twUH;
         p.planH = P->planH; p.planUH = P->planUH;
         p.W = (int)P->W; p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.zly = P->zly; p.zry = P->zry;
         p.inv_norm = (S)(1.0 / (double)P->uH);
-        columns_kernel<C>(P, [&](auto k, const auto&... z) { launch(k, dim3(P->NT, 3), st, p, z...); });
+        columns_kernel<C>(P, [&](auto k, const auto&... z) { launch(k, dim3(P->NT, 3), f.st, p, z...); });
         return;
     }
     Row4Params<C> q{};
-    const fftup_plan::Four &f = P->colF, &g = P->colI;
-    q.spec = (const C*)P->lanes[P->cur].S1; q.T = (C*)P->lanes[P->cur].T4; q.R = P->lanes[P->cur].S1;
-    q.tw1 = (const C*)P->colFtw.tw1; q.tw2 = (const C*)P->colFtw.tw2; q.twN = (const C*)P->twH; q.plan1 = f.p1; q.plan2 = f.p2;
-    q.N = (int)P->H; q.N1 = f.n1; q.N2 = f.n2; q.rows = P->ncols; q.W = (int)P->H; q.TK = 1; q.NT = P->ncols; q.inv_norm = (S)1;
-    launch_four(four_col_kernels<C>(P, false), f, q, P->ncols, st);
-    q.R = P->lanes[P->cur].S2; q.tw1 = (const C*)P->colItw.tw1; q.tw2 = (const C*)P->colItw.tw2; q.twN = (const C*)P->twUH; q.plan1 = g.p1; q.plan2 = g.p2;
+    const fftup_plan::Four &s = P->colF, &g = P->colI;
+    q.spec = (const C*)f.S1; q.T = (C*)f.T4; q.R = f.S1;
+    q.tw1 = (const C*)P->colFtw.tw1; q.tw2 = (const C*)P->colFtw.tw2; q.twN = (const C*)P->twH; q.plan1 = s.p1; q.plan2 = s.p2;
+    q.N = (int)P->H; q.N1 = s.n1; q.N2 = s.n2; q.rows = P->ncols; q.W = (int)P->H; q.TK = 1; q.NT = P->ncols; q.inv_norm = (S)1;
+    launch_four(four_col_kernels<C>(P, false), s, q, P->ncols, f.st);
+    q.R = f.S2; q.tw1 = (const C*)P->colItw.tw1; q.tw2 = (const C*)P->colItw.tw2; q.twN = (const C*)P->twUH; q.plan1 = g.p1; q.plan2 = g.p2;
     q.N = (int)P->uH; q.N1 = g.n1; q.N2 = g.n2; q.zlx = P->zly; q.zrx = P->zry; q.inv_norm = (S)(1.0 / (double)P->uH);
-    launch_four(four_col_kernels<C>(P, true), g, q, P->ncols, st);
+    launch_four(four_col_kernels<C>(P, true), g, q, P->ncols, f.st);
 }
 
 // ---- -p 1: the size-generic kernels instantiated on double2 + the double sharpen
-static int launch_frame_f64(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+static int launch_frame_f64(const fftup_plan* P, const Frame& f, Pass pass)
 {
-    hipStream_t st = P->lanes[P->cur].stream;
-    if (which < 0 || which == 0) {
+    if (runs(pass, Pass::rows)) {
         RowR2CParamsT<double2> p{};
-        p.S1 = (double2*)P->lanes[P->cur].S1; p.tw = (const double2*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        p.S1 = (double2*)f.S1; p.tw = (const double2*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         p.TK = P->TK; p.NT = P->NT;
-        set_in(P, in_slot, 1, p);
-        launch(f64_row_kernel(P), dim3(P->H / 2, 3), st, p);
+        set_in(f, p);
+        launch(f64_row_kernel(P), dim3(P->H / 2, 3), f.st, p);
     }
-    if (which < 0 || which == 1) launch_columns<double2>(P, st);
-    if (which < 0 || which == 2) {
+    if (runs(pass, Pass::columns)) launch_columns<double2>(P, f);
+    if (runs(pass, Pass::inverse)) {
         RowC2RParamsT<double2> p{};
-        p.S1 = (const double2*)P->lanes[P->cur].S1; p.S2 = (const double2*)P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = (const double2*)P->twUW; p.plan = P->planUW;
+        p.S1 = (const double2*)f.S1; p.S2 = (const double2*)f.S2; p.R = f.R; p.tw = (const double2*)P->twUW; p.plan = P->planUW;
         p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = P->zlx; p.zrx = P->zrx;
         p.inv_norm = 1.0 / (double)P->uW; p.poly = P->poly;
-        launch(f64_c2r_kernel(P), dim3(P->uH / 2, 3), st, p);
+        launch(f64_c2r_kernel(P), dim3(P->uH / 2, 3), f.st, p);
     }
-    if (which < 0 || which == 3) {
+    if (runs(pass, Pass::sharpen)) {
         SharpenParams p{};
-        p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+        p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
         const dim3 sgrid((P->uW + 511) / 512, (P->uH + SHARPEN_F64_RPT - 1) / SHARPEN_F64_RPT, 3);
         const char* ex = fftup_jit::experiment("f64_exact_sharpen");          // (test builds: IEEE divisions and root)
         if (ex && atoi(ex)) {
-            if (P->uW % 2 == 0) hipLaunchKernelGGL((k_sharpen_f64<true, true>), sgrid, dim3(64, 4), 0, st, p);
-            else hipLaunchKernelGGL((k_sharpen_f64<false, true>), sgrid, dim3(64, 4), 0, st, p);
+            if (P->uW % 2 == 0) hipLaunchKernelGGL((k_sharpen_f64<true, true>), sgrid, dim3(64, 4), 0, f.st, p);
+            else hipLaunchKernelGGL((k_sharpen_f64<false, true>), sgrid, dim3(64, 4), 0, f.st, p);
         }
-        else if (P->uW % 2 == 0) hipLaunchKernelGGL(k_sharpen_f64<true>, sgrid, dim3(64, 4), 0, st, p);
-        else hipLaunchKernelGGL(k_sharpen_f64<false>, sgrid, dim3(64, 4), 0, st, p);
+        else if (P->uW % 2 == 0) hipLaunchKernelGGL(k_sharpen_f64<true>, sgrid, dim3(64, 4), 0, f.st, p);
+        else hipLaunchKernelGGL(k_sharpen_f64<false>, sgrid, dim3(64, 4), 0, f.st, p);
     }
     return frame_status();
 }
 
 // ---- non-R2C path: four launches of size-generic kernels on complex data; rows beyond one LDS buffer in four
 // steps through HBM
-template <typename C> static int launch_frame_cplx(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+template <typename C> static int launch_frame_cplx(const fftup_plan* P, const Frame& f, Pass pass)
 {
-    hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = frame_kind(P, in_slot);
     using S = scalar_t<C>;
-    if ((which < 0 || which == 0) && P->fourF.on) {
+    if (runs(pass, Pass::rows) && P->fourF.on) {
         Row4Params<C> q{};
-        const fftup_plan::Four& f = P->fourF;
-        q.T = (C*)P->lanes[P->cur].T4; q.S1 = (C*)P->lanes[P->cur].S1; q.tw1 = (const C*)P->fourFtw.tw1; q.tw2 = (const C*)P->fourFtw.tw2; q.twN = (const C*)P->twW;
-        q.plan1 = f.p1; q.plan2 = f.p2; q.N = (int)P->W; q.N1 = f.n1; q.N2 = f.n2; q.rows = (int)P->H; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT;
-        set_in(P, in_slot, kind, q);
-        launch_four(four_fwd_kernels<C>(P, kind), f, q, (int)P->H, st);
-    } else if (which < 0 || which == 0) {
+        const fftup_plan::Four& s = P->fourF;
+        q.T = (C*)f.T4; q.S1 = (C*)f.S1; q.tw1 = (const C*)P->fourFtw.tw1; q.tw2 = (const C*)P->fourFtw.tw2; q.twN = (const C*)P->twW;
+        q.plan1 = s.p1; q.plan2 = s.p2; q.N = (int)P->W; q.N1 = s.n1; q.N2 = s.n2; q.rows = (int)P->H; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT;
+        set_in(f, q);
+        launch_four(four_fwd_kernels<C>(P, f.kind), s, q, (int)P->H, f.st);
+    } else if (runs(pass, Pass::rows)) {
         RowR2CParamsT<C> p{};
-        p.S1 = (C*)P->lanes[P->cur].S1; p.tw = (const C*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+        p.S1 = (C*)f.S1; p.tw = (const C*)P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
         p.TK = P->TK; p.NT = P->NT;
-        set_in(P, in_slot, kind, p);
-        launch(c2c_fwd_kernel<C>(P, kind), dim3(P->H, 3), st, p);
+        set_in(f, p);
+        launch(c2c_fwd_kernel<C>(P, f.kind), dim3(P->H, 3), f.st, p);
     }
-    if (which < 0 || which == 1) launch_columns<C>(P, st);
-    if (which < 0 || which == 2) {
+    if (runs(pass, Pass::columns)) launch_columns<C>(P, f);
+    if (runs(pass, Pass::inverse)) {
         if (P->fourI.on) {
             Row4Params<C> q{};
-            const fftup_plan::Four& f = P->fourI;
-            q.spec = (const C*)P->lanes[P->cur].S2; q.T = (C*)P->lanes[P->cur].T4; q.R = P->lanes[P->cur].R;
-            q.tw1 = (const C*)P->fourItw.tw1; q.tw2 = (const C*)P->fourItw.tw2; q.twN = (const C*)P->twUW; q.plan1 = f.p1; q.plan2 = f.p2;
-            q.N = (int)P->uW; q.N1 = f.n1; q.N2 = f.n2; q.rows = (int)P->uH; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT; q.zlx = P->zlx; q.zrx = P->zrx;
+            const fftup_plan::Four& s = P->fourI;
+            q.spec = (const C*)f.S2; q.T = (C*)f.T4; q.R = f.R;
+            q.tw1 = (const C*)P->fourItw.tw1; q.tw2 = (const C*)P->fourItw.tw2; q.twN = (const C*)P->twUW; q.plan1 = s.p1; q.plan2 = s.p2;
+            q.N = (int)P->uW; q.N1 = s.n1; q.N2 = s.n2; q.rows = (int)P->uH; q.W = (int)P->W; q.TK = P->TK; q.NT = P->NT; q.zlx = P->zlx; q.zrx = P->zrx;
             q.inv_norm = (S)(1.0 / (double)P->uW);
-            launch_four(four_inv_kernels<C>(P), f, q, (int)P->uH, st);
+            launch_four(four_inv_kernels<C>(P), s, q, (int)P->uH, f.st);
         } else {
             RowC2RParamsT<C> p{};
-            p.S2 = (const C*)P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = (const C*)P->twUW; p.plan = P->planUW;
+            p.S2 = (const C*)f.S2; p.R = f.R; p.tw = (const C*)P->twUW; p.plan = P->planUW;
             p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = P->zlx; p.zrx = P->zrx;
             p.inv_norm = (S)(1.0 / (double)P->uW);
-            launch(c2c_inv_kernel<C>(P), dim3(P->uH, 3), st, p);
+            launch(c2c_inv_kernel<C>(P), dim3(P->uH, 3), f.st, p);
         }
-        P->R_valid = true;
     }
-    if (which < 0 || which == 3) {
+    if (runs(pass, Pass::sharpen)) {
         SharpenParams p{};
-        p.R = P->lanes[P->cur].R; p.out = frame_out(P, out_slot); p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+        p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
         const dim3 grid((P->uW + 255) / 256, P->uH, 3);
         bool done = false;
         if constexpr (sizeof(S) == 4) {
-            if (P->half) { hipLaunchKernelGGL((k_sharpen_c<C, true>), grid, dim3(256), 0, st, p); done = true; }
+            if (P->half) { hipLaunchKernelGGL((k_sharpen_c<C, true>), grid, dim3(256), 0, f.st, p); done = true; }
         }
-        if (!done) hipLaunchKernelGGL((k_sharpen_c<C>), grid, dim3(256), 0, st, p);
+        if (!done) hipLaunchKernelGGL((k_sharpen_c<C>), grid, dim3(256), 0, f.st, p);
     }
     return frame_status();
 }
 
 // ---- ahead-of-time plans: power-of-two sizes (kernels_pow2.hpp, kernels_dswap.hpp) and the two mixed-radix configurations
-// (kernels_mixed.hpp).  Fused C2R+sharpen unless FFTUP_FLAG_UNFUSED_SHARPEN; 22: the pre-sharpen tap of a fused plan
-static int launch_frame_tuned(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+// (kernels_mixed.hpp).  Fused C2R+sharpen unless FFTUP_FLAG_UNFUSED_SHARPEN; Pass::presharpen_tap runs the stand-alone C2R of a fused plan
+static int launch_frame_tuned(const fftup_plan* P, const Frame& f, Pass pass)
 {
-    hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = frame_kind(P, in_slot);
-    if (which < 0 || which == 0) {
+    if (runs(pass, Pass::rows)) {
         RowR2CTParams p{};
-        p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.H = (int)P->H; p.NT = P->NT;
-        set_in(P, in_slot, kind, p);
-        launch(tuned_row_kernel(P, kind), dim3(P->H / 2, pass_planes()), st, p);
+        p.S1 = f.S1; p.tw = P->twW; p.H = (int)P->H; p.NT = P->NT;
+        set_in(f, p);
+        launch(tuned_row_kernel(P, f.kind), dim3(P->H / 2, pass_planes()), f.st, p);
     }
-    if (which < 0 || which == 1) {
+    if (runs(pass, Pass::columns)) {
         ColTParams p{};
-        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.twH = P->twH; p.twUH = P->twUH; p.W = (int)P->W; p.NT = P->NT;
+        p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.twUH = P->twUH; p.W = (int)P->W; p.NT = P->NT;
         p.zly = P->zly; p.zry = P->zry;
-        launch(tuned_col_kernel(P), dim3(P->NT, pass_planes()), st, p);
+        launch(tuned_col_kernel(P), dim3(P->NT, pass_planes()), f.st, p);
     }
-    if ((which < 0 || which == 2) && P->fused) {
-        const FusedParams p = fused_params(P, out_slot);
-        launch(fused_kernel(P), dim3(fused_grid(P, p.pairs_per_strip)), st, p);
-        P->R_valid = false;
-    } else if (which < 0 || which == 2 || which == 22) {
+    if (runs(pass, Pass::inverse) && P->fused) {
+        const FusedParams p = fused_params(P, f);
+        launch(fused_kernel(P), dim3(fused_grid(P, p.pairs_per_strip)), f.st, p);
+    } else if (runs(pass, Pass::inverse) || pass == Pass::presharpen_tap) {
         RowC2RTParams p{};
-        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
-        launch(tuned_c2r_kernel(P), dim3(P->uH / 2, 3), st, p);
-        P->R_valid = true;
+        p.S1 = f.S1; p.S2 = f.S2; p.R = f.R; p.tw = P->twUW; p.uH = (int)P->uH; p.NT = P->NT;
+        launch(tuned_c2r_kernel(P), dim3(P->uH / 2, 3), f.st, p);
     }
-    if ((which < 0 || which == 3) && !P->fused) launch_sharpen_fast(P, out_slot);
+    if (runs(pass, Pass::sharpen) && !P->fused) launch_sharpen_fast(P, f);
     return frame_status();
 }
 
 // ---- the size-generic R2C plans on fp32 / fp16 data (kernels_generic.hpp; FFTUP_FLAG_ANY_SIZE: kernels_bluestein.hpp, odd_rows) and the
 // mixed-radix plans: ahead of time (kernels_mixed.hpp) or specialised at plan time -- those are launched from P->jit as it is NOW
 // (the tuner swaps it after plan creation)
-static int launch_frame_generic(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+static int launch_frame_generic(const fftup_plan* P, const Frame& f, Pass pass)
 {
-    hipStream_t st = P->lanes[P->cur].stream;
-    const int kind = frame_kind(P, in_slot);
     const bool jit = P->family == Family::mixed_jit, aot = P->family == Family::mixed_aot;
     hipError_t jerr = hipSuccess;
     auto keep_first = [&](hipError_t e) { if (jerr == hipSuccess) jerr = e; };       // (later launches must not mask an earlier failure)
-    if (which < 0 || which == 0) {
+    if (runs(pass, Pass::rows)) {
         const dim3 grid(P->H / 2, 3);
-        if (resampling_rows(P)) odd_rows(P, in_slot, kind, st);
+        if (resampling_rows(P)) odd_rows(P, f);
         else if (aot || (jit && P->jit->choice.row_kind != 2)) {
             RowR2CTParams q{};
-            q.S1 = P->lanes[P->cur].S1; q.tw = P->twW; q.H = (int)P->H; q.NT = P->NT;
-            set_in(P, in_slot, kind, q);
-            if (aot) launch(mixed_row_kernel(P, kind), grid, st, q);
-            else keep_first(fftup_jit::launch(P->jit->fn[kind == 2 ? fftup_jit::K_ROW_U8 : fftup_jit::K_ROW_PLANAR], grid, dim3(P->jit->choice.row_block), 0, st, q));
+            q.S1 = f.S1; q.tw = P->twW; q.H = (int)P->H; q.NT = P->NT;
+            set_in(f, q);
+            if (aot) launch(mixed_row_kernel(P, f.kind), grid, f.st, q);
+            else keep_first(fftup_jit::launch(P->jit->fn[f.kind == 2 ? fftup_jit::K_ROW_U8 : fftup_jit::K_ROW_PLANAR], grid, dim3(P->jit->choice.row_block), 0, f.st, q));
         } else {
             RowR2CParams p{};
-            p.S1 = P->lanes[P->cur].S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+            p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
             p.TK = P->TK; p.NT = P->NT;
-            set_in(P, in_slot, kind, p);
-            launch(generic_row_kernel(P, kind), grid, st, p);
+            set_in(f, p);
+            launch(generic_row_kernel(P, f.kind), grid, f.st, p);
         }
     }
-    if ((which < 0 || which == 1) && (jit || aot)) {
+    if (runs(pass, Pass::columns) && (jit || aot)) {
         ColTParams q{};
-        q.S1 = P->lanes[P->cur].S1; q.S2 = P->lanes[P->cur].S2; q.twH = P->twH; q.twUH = P->twUH; q.W = (int)P->W; q.NT = P->NT;
+        q.S1 = f.S1; q.S2 = f.S2; q.twH = P->twH; q.twUH = P->twUH; q.W = (int)P->W; q.NT = P->NT;
         q.zly = P->zly; q.zry = P->zry;
         if (jit) {
             const auto& ch = P->jit->choice;
             const dim3 jgrid(P->NT * (ch.col_kind >= 3 ? 4 / ch.col_cols : 1), 3);        // (long columns: two per workgroup)
-            keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_COL], jgrid, dim3(ch.col_block), P->ldsCol, st, q));
+            keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_COL], jgrid, dim3(ch.col_block), P->ldsCol, f.st, q));
         }
-        else launch(mixed_col_kernel(P), dim3(P->NT, 3), st, q);
+        else launch(mixed_col_kernel(P), dim3(P->NT, 3), f.st, q);
     }
-    else if (which < 0 || which == 1) launch_columns<float2>(P, st);
-    if ((which < 0 || which == 2) && P->fused) {
-        const FusedParams fp = fused_params(P, out_slot);
+    else if (runs(pass, Pass::columns)) launch_columns<float2>(P, f);
+    if (runs(pass, Pass::inverse) && P->fused) {
+        const FusedParams fp = fused_params(P, f);
         const dim3 grid(fused_grid(P, fp.pairs_per_strip));
-        if (jit) keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_FUSED], grid, dim3(P->jit->choice.fused_t), P->jit->choice.fused_lds, st, fp));
-        else launch(fused_kernel(P), grid, st, fp);                      // (only the mixed plans are fused on this path)
-        P->R_valid = false;
-    } else if (which < 0 || which == 2 || which == 22) {
+        if (jit) keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_FUSED], grid, dim3(P->jit->choice.fused_t), P->jit->choice.fused_lds, f.st, fp));
+        else launch(fused_kernel(P), grid, f.st, fp);                    // (only the mixed plans are fused on this path)
+    } else if (runs(pass, Pass::inverse) || pass == Pass::presharpen_tap) {
         RowC2RParams p{};
-        p.S1 = P->lanes[P->cur].S1; p.S2 = P->lanes[P->cur].S2; p.R = P->lanes[P->cur].R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->W; p.uW = (int)P->uW;
+        p.S1 = f.S1; p.S2 = f.S2; p.R = f.R; p.tw = P->twUW; p.plan = P->planUW; p.W = (int)P->W; p.uW = (int)P->uW;
         p.uH = (int)P->uH; p.TK = P->TK; p.NT = P->NT; p.zlx = P->zlx; p.zrx = P->zrx;
         p.inv_norm = 1.0f / (float)P->uW; p.poly = P->poly && !P->mixed;
         const dim3 grid(P->uH / 2, 3);
         if (jit) {
             if (P->U == 1) p.S1 = p.S2;                              // half-integer factor: all rows in S2
-            keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_C2R_CT], grid, dim3(P->jit->choice.ct_t), P->ldsRowI, st, p));
+            keep_first(fftup_jit::launch(P->jit->fn[fftup_jit::K_C2R_CT], grid, dim3(P->jit->choice.ct_t), P->ldsRowI, f.st, p));
         }
-        else if (aot) launch(mixed_c2r_kernel(P), grid, st, p);
-        else generic_c2r_kernel(P, [&](auto k, const auto&... z) { launch(k, grid, st, p, z...); });
-        P->R_valid = true;
+        else if (aot) launch(mixed_c2r_kernel(P), grid, f.st, p);
+        else generic_c2r_kernel(P, [&](auto k, const auto&... z) { launch(k, grid, f.st, p, z...); });
     }
-    if ((which < 0 || which == 3) && !P->fused) launch_sharpen(P, out_slot);
+    if (runs(pass, Pass::sharpen) && !P->fused) launch_sharpen(P, f);
     return frame_status(jerr);
 }
 
-int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which)
+static int launch_family(const fftup_plan* P, const Frame& f, Pass pass)
 {
-    if (frame_kind(P, in_slot) == 0 && which != 22) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (22, the pre-sharpen tap, reads spectra only)
     switch (P->family) {
-    case Family::cplx: return P->dbl ? launch_frame_cplx<double2>(P, in_slot, out_slot, which) : launch_frame_cplx<float2>(P, in_slot, out_slot, which);
-    case Family::f64: return launch_frame_f64(P, in_slot, out_slot, which);
-    case Family::dct: return launch_four_passes(P, in_slot, out_slot, which, dct_rows, dct_cols, dct_inv);
-    case Family::down: return launch_four_passes(P, in_slot, out_slot, which, down_rows, down_cols, down_inv);
-    case Family::odd: return launch_four_passes(P, in_slot, out_slot, which, odd_rows, odd_cols, odd_inv);
-    case Family::view: return launch_four_passes(P, in_slot, out_slot, which, odd_rows, view_cols, view_inv);
-    case Family::tuned: return launch_frame_tuned(P, in_slot, out_slot, which);
+    case Family::cplx: return P->dbl ? launch_frame_cplx<double2>(P, f, pass) : launch_frame_cplx<float2>(P, f, pass);
+    case Family::f64: return launch_frame_f64(P, f, pass);
+    case Family::dct: return launch_four_passes(P, f, pass, dct_rows, dct_cols, dct_inv);
+    case Family::down: return launch_four_passes(P, f, pass, down_rows, down_cols, down_inv);
+    case Family::odd: return launch_four_passes(P, f, pass, odd_rows, odd_cols, odd_inv);
+    case Family::view: return launch_four_passes(P, f, pass, odd_rows, view_cols, view_inv);
+    case Family::tuned: return launch_frame_tuned(P, f, pass);
     case Family::generic: case Family::mixed_aot: case Family::mixed_jit: break;
     }
-    return launch_frame_generic(P, in_slot, out_slot, which);
+    return launch_frame_generic(P, f, pass);
+}
+int launch_frame(fftup_plan* P, const FrameRun& r)
+{
+    const Frame f = resolve(P, r);
+    const bool tap = r.pass == Pass::presharpen_tap;
+    if (f.kind == 0 && !tap) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (the tap reads spectra only)
+    const int rc = launch_family(P, f, r.pass);
+    // what the frame left: its inverse rows have run, so the tap reads this lane's spectra, or its R unless the fused kernel ran instead
+    if (tap || runs(r.pass, Pass::inverse)) { P->last_lane = r.lane; P->R_valid = !(P->fused && !tap); }
+    return rc;
 }
 
 // 64-bit wrapping sum of 32-bit words (fftup_output_checksum): per-thread partial sums, wave reduction, one atomic per wave

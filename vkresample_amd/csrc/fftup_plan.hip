@@ -242,30 +242,25 @@ static int make_buffers(fftup_plan* P)
         if (int rc = dev_alloc(P, (void**)&P->in_u8[s], (size_t)3 * P->W * P->H)) return rc;
         if (int rc = dev_alloc(P, &P->out[s], out_pixels * (P->u8out ? 1 : esz) + 8)) return rc;          // (+ 8: readers of whole words)
     }
-    if (int rc = alloc_spectra(P, &P->S1, &P->S2)) return rc;
-    // the pre-sharpen image (the reference's tempBuffer): every frame of an unfused plan goes through it; a fused plan
-    // only needs one for the fftup_download_presharpen tap, which allocates it on first use (ensure_R)
     P->r_bytes = out_pixels * (P->cplx ? (P->half ? 4 : P->csz) : esz);  // non-R2C path: complex pre-sharpen image (binary16 pairs for -p 2)
-    if (!P->fused)
-        if (int rc = dev_alloc(P, &P->R, P->r_bytes)) return rc;
     if (!P->u8out)
         if (int rc = dev_alloc(P, (void**)&P->out_u8, out_pixels + 8)) return rc;   // staging of the conversion launch (+ 8: k_png_filter reads whole words)
     return FFTUP_OK;
 }
 
-// the streams consecutive frames alternate on: lane 0 = the plan's own stream and buffers, every other lane its own
+// the streams consecutive frames alternate on: lane 0 runs on the plan's own stream, every other lane on its own; each lane has
+// its spectra and its completion event.  The pre-sharpen image R (the reference's tempBuffer): every frame of an unfused plan
+// goes through it; a fused plan only needs one for the fftup_download_presharpen tap, which allocates it on first use
 static int make_lanes(fftup_plan* P)
 {
     P->nlanes = lane_count();
     P->lanes.resize(P->nlanes);
-    P->lanes[0].stream = P->stream; P->lanes[0].S1 = P->S1; P->lanes[0].S2 = P->S2; P->lanes[0].R = P->R;
     const size_t t4_bytes = P->csz * 3 * std::max(std::max(P->fourF.on ? (size_t)P->W * P->H : 0, P->fourI.on ? (size_t)P->uW * P->uH : 0),
                                                   P->colI.on ? (size_t)P->ncols * P->uH : 0);
-    if (t4_bytes)
-        if (int rc = dev_alloc(P, &P->lanes[0].T4, t4_bytes)) return rc;
-    for (int l = 1; l < P->nlanes; l++) {
+    for (int l = 0; l < P->nlanes; l++) {
         fftup_plan::Lane& lane = P->lanes[l];
-        HIP_TRY(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
+        if (l == 0) lane.stream = P->stream;
+        else HIP_TRY(hipStreamCreateWithFlags(&lane.stream, hipStreamNonBlocking));
         HIP_TRY(hipEventCreateWithFlags(&lane.done, hipEventDisableTiming));
         if (int rc = alloc_spectra(P, &lane.S1, &lane.S2)) return rc;
         if (!P->fused)
@@ -368,8 +363,8 @@ void fftup_plan_destroy(fftup_plan* P)
     if (!P) return;
     (void)hipSetDevice(P->device);
     if (P->stream) (void)hipStreamSynchronize(P->stream);
-    for (size_t l = 1; l < P->lanes.size(); l++) {
-        if (P->lanes[l].stream) { (void)hipStreamSynchronize(P->lanes[l].stream); (void)hipStreamDestroy(P->lanes[l].stream); }
+    for (size_t l = 0; l < P->lanes.size(); l++) {           // (lane 0's stream is the plan's own: destroyed below)
+        if (l && P->lanes[l].stream) { (void)hipStreamSynchronize(P->lanes[l].stream); (void)hipStreamDestroy(P->lanes[l].stream); }
         if (P->lanes[l].done) (void)hipEventDestroy(P->lanes[l].done);
     }
     for (auto& qs : P->q) {
@@ -380,7 +375,6 @@ void fftup_plan_destroy(fftup_plan* P)
     }
     if (P->png_copy) (void)hipStreamDestroy(P->png_copy);
     if (P->dio.start) (void)hipEventDestroy(P->dio.start);
-    for (hipEvent_t e : P->dio.done) if (e) (void)hipEventDestroy(e);
     for (void* p : P->allocs) (void)hipFree(p);
     delete P->jit;
     if (P->ev0) (void)hipEventDestroy(P->ev0);

@@ -141,11 +141,7 @@ int submit_frame(fftup_plan* P, const uint8_t* rgb_in, size_t in_stride, uint8_t
             launch_unpack(P, s, cs);
             P->in_kind[s] = 1;
         }
-        P->cur = lane;
-        const int frc = launch_frame(P, s, s, -1);
-        P->last_lane = lane;
-        P->cur = 0;
-        if (frc) return frc;
+        if (const int frc = launch_frame(P, {lane, s, P->out[s]})) return frc;
         if (!P->u8out) launch_pack(P, s, Q.out_u8, cs);
         HIP_TRY(hipGetLastError());
         if (png) return png_enqueue(P, Q, cs, png_dest);

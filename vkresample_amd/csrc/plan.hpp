@@ -16,6 +16,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <cstdint>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -71,21 +72,22 @@ struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what li
     fftup_view vw{};
     struct ViewAxis { int kmax = 0; uint32_t L = 0; StagePlan planL{}; float2 *tw = nullptr, *pre = nullptr, *post = nullptr, *bhat = nullptr; };
     ViewAxis vx, vy;
-    bool R_valid = false;             // pre-sharpen buffer holds the last frame (unfused path only)
+    bool R_valid = false;             // lanes[last_lane].R holds the last frame (a fused plan: only after the pre-sharpen tap has run)
 
     // device memory
     std::vector<void*> in_planar;     // per slot: planar float/half, row stride W, plane stride (W+2)*H
     std::vector<uint8_t*> in_u8;      // per slot: RGB u8 [H][W][3] (staging and fused-load source)
     std::vector<int> in_kind;         // per slot: 0 none, 1 planar valid, 2 u8 valid (fused)
-    float2 *S1 = nullptr, *S2 = nullptr;
-    void* R = nullptr;                // pre-sharpen, dense [3][uH][uW]
     // batched mode runs consecutive frames on `nlanes` streams (the reference's -numthreads does the same with
-    // several queues on one device); every lane owns its scratch spectra.  Lane 0 = the members above.
+    // several queues on one device); every lane owns its scratch spectra, its pre-sharpen image R (dense [3][uH][uW]) and the
+    // event that joins it to other streams (lanes_join; timing disabled; lane 0 has one too, for fftup_execute_device, which
+    // therefore keeps no event set of its own).  Lane 0 runs on the plan's own stream.
     struct Lane { hipStream_t stream = nullptr; float2 *S1 = nullptr, *S2 = nullptr; void* R = nullptr; hipEvent_t done = nullptr;
                   void* T4 = nullptr; };             // T4: the four-step rows' transposition buffer
     std::vector<Lane> lanes;
-    int nlanes = 1, cur = 0, last_lane = 0;
-    std::vector<void*> out;           // per slot: dense [3][uH][uW]
+    int nlanes = 1;
+    int last_lane = 0;                // the lane of the last frame whose inverse rows ran -- with R_valid, written by launch_frame alone
+    std::vector<void*> out;           // per slot: dense [3][uH][uW]; behind the ring's slots the extra images of fftup_execute
     uint8_t* out_u8 = nullptr;        // staging for download_rgb8
     // host-streamed queue (fftup_submit_rgb8): created on first use
     // (png: the device-side PNG encoder's buffers of the slot, created on the first fftup_submit_png; state 1 = a stream waits for
@@ -112,13 +114,9 @@ struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what li
     size_t in_plane_stride = 0;
     int executed = 0;
 
-    // fftup_execute_device: while `io` is set the frame being launched reads `in` (kind 1: planes, strides in elements; kind 2:
-    // 8-bit RGB, row stride in bytes) and its last kernel writes `out` -- caller memory or the lane's staging -- instead of ring slots
-    struct FrameIO { const void* in = nullptr; int kind = 0; long in_row = 0, in_plane = 0; void* out = nullptr; };
-    const FrameIO* io = nullptr;
-    // created by the first call that needs them: one start event, one completion event per lane; per lane the staging planes
-    // (the in_planar layout) and the scratch image (the layout of an output slot) of the layouts that cannot run in place
-    struct DeviceIO { hipEvent_t start = nullptr; std::vector<hipEvent_t> done; std::vector<void*> stage_in, scratch_out; };
+    // fftup_execute_device, created by the first call that needs them: the start event (timing disabled, unlike ev0); per lane the
+    // staging planes (the in_planar layout) and the scratch image (the layout of an output slot) of the layouts that cannot run in place
+    struct DeviceIO { hipEvent_t start = nullptr; std::vector<void*> stage_in, scratch_out; };
     DeviceIO dio;
     bool dev_executed = false;        // a frame of fftup_execute_device has run: the pre-sharpen tap is valid, the slots are not
 
@@ -143,8 +141,16 @@ inline int check_slot(fftup_plan* P, uint32_t slot)
 // ---- fftup_launch.hip: everything that names a kernel (each instantiation once, in the selector of its pass and family)
 // (the facts about the kernels the planner needs: plan_rules.hpp)
 int kernels_set_attributes(fftup_plan* P);                        // dynamic LDS sizes above 64 KB, for the kernels launch_frame's selectors give THIS plan
-// one frame on lane P->cur: `which` < 0 launches all of its kernels, 0..3 only that one, 22 = the pre-sharpen tap of a fused plan
-int launch_frame(fftup_plan* P, uint32_t in_slot, uint32_t out_slot, int which);
+// One frame: its caller names all of it in a FrameRun, nothing about the frame being launched lives in the plan.  Pass: rows ..
+// sharpen are the indices of fftup_profile_kernels / fftup_execute_ring_timed; presharpen_tap = the stand-alone inverse rows of
+// a fused plan, from the lane's spectra into its R.  DeviceInput (fftup_execute_device): input outside the ring -- caller memory
+// or a lane's staging (kind 1: planes, strides in elements; kind 2: 8-bit RGB, row stride in bytes)
+enum class Pass { rows, columns, inverse, sharpen, all, presharpen_tap };
+struct DeviceInput { const void* in = nullptr; int kind = 0; long in_row = 0, in_plane = 0; };
+// in_slot: the ring slot the frame reads (`in`: instead of the slot); out: the image its last kernel writes -- a slot's, an extra
+// one of fftup_execute, caller memory, a lane's scratch
+struct FrameRun { int lane = 0; uint32_t in_slot = 0; void* out = nullptr; const DeviceInput* in = nullptr; Pass pass = Pass::all; };
+int launch_frame(fftup_plan* P, const FrameRun& r);               // launches, then records what the frame left: the only writer of last_lane and R_valid (but see fftup_execute)
 void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st);                  // the host loop of VR:1636-1685 as a kernel
 void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st);      // ... and of VR:1708-1748
 void launch_checksum(fftup_plan* P, uint32_t slot, hipStream_t st);                // 64-bit sum of the slot's words -> P->d_sum
@@ -157,6 +163,11 @@ void launch_copy_rows(const void* src, size_t src_row, size_t src_plane, void* d
                       size_t row_bytes, uint32_t rows, uint32_t planes, int gran, hipStream_t st);
 
 // ---- fftup_execute.hip
+// fork: the lanes [first, nl) go on behind what `from` holds now (`ev` is recorded on it).  join: each of them records its `done`
+// event and every stream of `into` waits for it (a stream never for itself); `rc` is the status so far, which an event failure
+// does not replace
+int lanes_fork(fftup_plan* P, hipEvent_t ev, hipStream_t from, int first, int nl);
+int lanes_join(fftup_plan* P, int first, int nl, std::initializer_list<hipStream_t> into, int rc);
 int execute_ring_impl(fftup_plan* P, uint32_t n_frames, uint32_t first_slot, double* ms_total, double* kernel_ms, uint32_t stride);
 
 // ---- fftup_queue.hip
