@@ -128,7 +128,7 @@ enum {
                                         decided before any device access.  fftup_jit_check keeps returning FFTUP_E_UNSUPPORTED_SIZE
                                         for these sizes, and fftup_version() is unchanged: detect the mode by creating a plan -- a
                                         library without it returns FFTUP_E_UNSUPPORTED_SIZE for 46x22 with the flag set         */
-    FFTUP_FLAG_ODD_SIZE = 2048u      /* EXTENSION: accepts odd widths and heights, input or output, and changes nothing else.
+    FFTUP_FLAG_ODD_SIZE = 2048u,     /* EXTENSION: accepts odd widths and heights, input or output, and changes nothing else.
                                         Without the flag: an odd W, H, uW or uH is FFTUP_E_INVALID_ARG, as before (also with
                                         FFTUP_FLAG_ANY_SIZE alone).  With it, on a plan whose four lengths are even: a no-op -- same
                                         kernels (ahead-of-time and plan-time ones included), same fftup_info, same output bytes.
@@ -162,6 +162,40 @@ enum {
                                         FFTUP_E_UNSUPPORTED_SIZE for these sizes, and fftup_version() is unchanged: detect the mode
                                         by creating a plan -- a library without it returns FFTUP_E_INVALID_ARG for 45x21 -u 2 with
                                         the flag set                                                                            */
+    FFTUP_FLAG_MIRROR = 4096u        /* EXTENSION: a view plan (fftup_plan_create_view, below) WITHOUT the wrap-around border.  Valid
+                                        on fftup_plan_create_view only; fftup_plan_set_view keeps working on such a plan.  Per axis,
+                                        separable.  The input is x[n], n < N.  The output has M points.  The view is (origin, span)
+                                        with step s = span / M.  Output pixel m sits at t_m = origin + m s.
+                                        With FFTUP_FLAG_MIRROR the frame is continued by its half-sample even reflection:
+                                        x~[n] = x[n] for n < N, x~[n] = x[2N-1-n] for N <= n < 2N, with period 2N.  The plan
+                                        evaluates the view formula of that extended frame.  In closed form:
+                                          C[k]  = sum_n x[n] cos(pi k (2n+1) / 2N)                         (DCT-II, k = 0 .. N-1)
+                                          kmax  = min(N - 1, floor((double)(N M) / max(span, (double)M)))
+                                          y[m]  = C[0]/N + (2/N) sum_{k=1..kmax} C[k] cos(pi k (2 t_m + 1) / 2N)
+                                        This equals the view formula below at period 2N applied to x~.  Bin N of the extension is
+                                        identically zero, so capping kmax at N-1 changes nothing.  Constants stay constant; a view
+                                        that touches a border mixes in the frame's own reflection instead of the opposite border,
+                                        and a view with origin < 0 or span > N shows reflected copies of the frame instead of
+                                        wrapped ones.  With origin = (N/M - 1)/2 and span = N it is FFTUP_FLAG_DCT's map (that
+                                        flag's upscale formula for M >= N, its downscale formula for M < N).
+                                        The pre-sharpen image is R = y span_x span_y / (uW uH).  The effective factor is u_e, as
+                                        for every view plan.  The sharpen pass is the view plans' own, unchanged, with quirks B4
+                                        and B5.
+                                        Rules, all arithmetic on the sizes and decided before any device access:
+                                        fftup_plan_create and fftup_plan_create_size return FFTUP_E_INVALID_ARG with the flag set;
+                                        with FFTUP_FLAG_DCT the view plans' FFTUP_E_UNSUPPORTED_SIZE stays; -p 1 is
+                                        FFTUP_E_UNSUPPORTED_PRECISION; width <= 8192; the step stays in [1/64, 8];
+                                        FFTUP_FLAG_ANY_SIZE keeps its meaning for width and height (the forward transforms stay
+                                        at lengths W and H -- the DCT-II of N points runs as ONE transform of N points -- Bluestein
+                                        where non-smooth, <= 4096).  The convolution lengths are those of the doubled period: the
+                                        smallest 2,3,5,7-smooth L >= 2N + M per axis.  Rows need L_x <= 8192 (1920 -> 3840: 7680,
+                                        2048 -> 4096: 8192), columns two local-memory buffers of max(H or its Bluestein length,
+                                        L_y) points at a tile width of 1: FFTUP_E_UNSUPPORTED_SIZE otherwise.
+                                        Four launches (fftup_info.tuned = u8_store = 0; kernel names row_r2c_mirror[_bz],
+                                        col_view_mirror[_bz], row_view_c2r_mirror, sharpen; fftup_plan_describe says "mirror");
+                                        every execution path works on such a plan unchanged.  A library without the mode ignores
+                                        the bit and returns the periodic view: detect the mode by kernel names carrying "_mirror",
+                                        fftup_version() is unchanged                                                             */
 };
 
 /* Replaces VkResampleConfiguration (VR:45-59) + the part of VkFFTConfiguration (VF:22-94) that

@@ -20,6 +20,7 @@ FLAG_DCT = 256                    # DCT-II -> zero-pad -> DCT-III instead of the
 FLAG_DOWNSCALE = 512              # upscale in [1/8, 1): spectrum cropped (older libraries refuse such plans: FFTUP_E_INVALID_ARG)
 FLAG_ANY_SIZE = 1024              # even lengths with a prime factor above 7, up to 4096: Bluestein transforms (older libraries: FFTUP_E_UNSUPPORTED_SIZE)
 FLAG_ODD_SIZE = 2048              # odd widths and heights: exact trigonometric resampling per axis (older libraries: FFTUP_E_INVALID_ARG)
+FLAG_MIRROR = 4096                # view plans only: the frame continued by its half-sample even reflection, no wrap at the borders (older libraries ignore the bit)
 
 # fftup_plan_create_size: where the output pixels sit
 ALIGN_CORNER = 0                  # output pixel 0 on input pixel 0, as every other FFT plan

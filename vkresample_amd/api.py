@@ -64,7 +64,8 @@ class Upscaler:
         """A view plan (fftup_plan_create_view): the out_width x out_height output shows the rectangle of the frame that starts at
         input position origin = (x, y) and is span = (w, h) input pixels wide and high -- output pixel m of an axis at origin + m span / M,
         any real numbers (zoom, sub-pixel pan, any ratio; the frame is periodic).  view_of_rect gives (origin, span) of a rectangle in
-        pixel-edge coordinates.  set_view re-aims the plan."""
+        pixel-edge coordinates.  set_view re-aims the plan.  flags=FLAG_MIRROR: the frame is continued by its half-sample even
+        reflection instead of periodically -- a view at a border does not mix in the opposite border (kernel names carry "_mirror")."""
         self = cls.__new__(cls)
         self._create(width, height, 1.0, precision, sharpen, device, flags, ring, (out_width, out_height), (origin, span))
         return self

@@ -23,6 +23,7 @@
 //   -centres      with -size: pixel centres aligned (FFTUP_ALIGN_CENTRE) instead of pixel 0 on pixel 0
 //   -view ox,oy,sx,sy  with -size: fftup_plan_create_view -- the output shows the rectangle of the frame that starts at input position
 //                 (ox, oy) and spans (sx, sy) input pixels: zoom, sub-pixel pan, any real ratio (the frame is periodic)
+//   -mirror       with -size and -view: FFTUP_FLAG_MIRROR -- the frame is continued by its reflection instead: no wrap at the borders
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -374,6 +375,7 @@ int main(int argc, char* argv[])
         printf("	-size WxH: the exact output size instead of -u, e.g. -size 1920x1080 on 1366x768: one factor per axis, each between 1/8 and 8, up or down (exact trigonometric resampling; -p 0 and -p 2, not with -dct or -u; -anysize for lengths with prime factors above 7)\n");
         printf("	-centres: with -size: align the pixel centres, as other resizers do (default: output pixel 0 on input pixel 0)\n");
         printf("	-view OX,OY,SX,SY: with -size: show the rectangle of the image that starts at position (OX, OY) and spans SX x SY input pixels, e.g. -size 1920x1080 -view 480,270,960,540 on 1920x1080: a 2x zoom about the centre; any real numbers (sub-pixel pan, any ratio; the image is periodic; a step SX/W outside [1/64, 8] is refused; not with -centres)\n");
+        printf("	-mirror: with -size and -view: continue the image by its reflection instead of periodically: no wrap-around at the borders, e.g. -size 1920x1080 -view -0.144,-0.144,1366,768 -mirror -anysize on 1366x768 (-p 0 and -p 2, not with -dct)\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -443,6 +445,10 @@ int main(int argc, char* argv[])
     if (findFlag(B, E, "-anysize")) config.flags |= FFTUP_FLAG_ANY_SIZE;
     if (findFlag(B, E, "-oddsize")) config.flags |= FFTUP_FLAG_ODD_SIZE;
     if (findFlag(B, E, "-downscale")) config.flags |= FFTUP_FLAG_DOWNSCALE;
+    if (findFlag(B, E, "-mirror")) {
+        if (!config.hasView) { printf("-mirror needs a view given with -size and -view\n"); return 1; }
+        config.flags |= FFTUP_FLAG_MIRROR;
+    }
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");
 

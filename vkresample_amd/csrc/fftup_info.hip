@@ -63,9 +63,9 @@ int fftup_plan_describe(const fftup_plan* P, char* buf, size_t buflen)
             + " (LDS ping-pong, run-time radix lists, column tiles of " + tiles + " column pairs)" + half;
         break;
     case Family::view: {
-        char t[256];
-        snprintf(t, sizeof t, "view: chirp-z resampling, rows %u->%u origin %.17g span %.17g (kmax %d, L=%u), columns %u->%u origin %.17g span %.17g (kmax %d, L=%u)",
-                 P->W, P->uW, P->vw.origin_x, P->vw.span_x, P->vx.kmax, P->vx.L, P->H, P->uH, P->vw.origin_y, P->vw.span_y, P->vy.kmax, P->vy.L);
+        char t[320];
+        snprintf(t, sizeof t, "view%s: chirp-z resampling, rows %u->%u origin %.17g span %.17g (kmax %d, L=%u), columns %u->%u origin %.17g span %.17g (kmax %d, L=%u)",
+                 P->mirror ? ", mirror (even reflection, period 2N)" : "", P->W, P->uW, P->vw.origin_x, P->vw.span_x, P->vx.kmax, P->vx.L, P->H, P->uH, P->vw.origin_y, P->vw.span_y, P->vy.kmax, P->vy.L);
         s = t + resampled;
         break;
     }
@@ -176,9 +176,9 @@ int fftup_plan_info(const fftup_plan* P, fftup_info* info)
     if (P->family == fftup_plan::Family::odd)
         for (int i = 0; i < 3; i++) strncat(info->kernel_names[i], "_odd", 63 - strlen(info->kernel_names[i]));
     if (P->family == fftup_plan::Family::view) {             // (kernels_view.hpp; the row R2C kernel is the odd-size plans')
-        snprintf(info->kernel_names[0], 64, "row_r2c_odd");
-        snprintf(info->kernel_names[1], 64, "col_view");
-        snprintf(info->kernel_names[2], 64, "row_view_c2r");
+        snprintf(info->kernel_names[0], 64, P->mirror ? "row_r2c_mirror" : "row_r2c_odd");
+        snprintf(info->kernel_names[1], 64, P->mirror ? "col_view_mirror" : "col_view");
+        snprintf(info->kernel_names[2], 64, P->mirror ? "row_view_c2r_mirror" : "row_view_c2r");
     }
     // kernels with a Bluestein transform (kernels_bluestein.hpp)
     const bool kbz[3] = {P->bzW.L != 0, P->bzH.L != 0 || P->bzUH.L != 0, P->bzUW.L != 0};

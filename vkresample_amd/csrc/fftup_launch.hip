@@ -28,6 +28,7 @@
 #include "kernels_bluestein.hpp"
 #include "kernels_odd.hpp"
 #include "kernels_view.hpp"
+#include "kernels_mirror.hpp"
 #include "kernels_device_io.hpp"
 
 using namespace fftup;
@@ -209,6 +210,13 @@ static bool resampling_rows(const fftup_plan* P) { return P->family == Family::g
 // fftup_plan_create_view (kernels_view.hpp)
 static Kern<ViewColParams> view_col_kernel(const fftup_plan* P) { return with_tile(P->TK, [&](auto tk) { return kern(k_col_view<tk()>, P->thrCol, P->ldsCol); }); }
 static Kern<ViewC2RParams> view_c2r_kernel(const fftup_plan* P) { return with_flag(P->half, [&](auto h) { return kern(k_row_view_c2r<h()>, P->thrUW, P->ldsRowI); }); }
+// ... with FFTUP_FLAG_MIRROR (kernels_mirror.hpp): the same three passes on kernels of their own, sized like the view plans'
+static Kern<MirrorRowParams> mirror_row_kernel(const fftup_plan* P, int kind)
+{
+    return with_mode(P->half, kind, [&](auto m) { return kern(k_row_r2c_mirror<m()>, P->thrW, P->ldsRowF); });
+}
+static Kern<MirrorColParams> mirror_col_kernel(const fftup_plan* P) { return with_tile(P->TK, [&](auto tk) { return kern(k_col_view_mirror<tk()>, P->thrCol, P->ldsCol); }); }
+static Kern<MirrorC2RParams> mirror_c2r_kernel(const fftup_plan* P) { return with_flag(P->half, [&](auto h) { return kern(k_row_view_c2r_mirror<h()>, P->thrUW, P->ldsRowI); }); }
 // ahead-of-time power-of-two plans (kernels_pow2.hpp, kernels_dswap.hpp: digit-swap column kernels, 4 KB of LDS per wave)
 static Kern<RowR2CTParams> tuned_row_kernel(const fftup_plan* P, int kind)
 {
@@ -313,7 +321,10 @@ int kernels_set_attributes(fftup_plan* P)
     case Family::dct: for (int kind : {1, 2}) allow(dct_row_kernel(P, kind)); allow(dct_col_kernel(P)); allow(idct_row_kernel(P)); break;
     case Family::down: for (int kind : {1, 2}) allow(crop_row_kernel(P, kind)); allow(crop_col_kernel(P)); generic_c2r_kernel(P, allow); break;
     case Family::odd: for (int kind : {1, 2}) allow(odd_row_kernel(P, kind)); allow(odd_col_kernel(P)); allow(odd_c2r_kernel(P)); break;
-    case Family::view: for (int kind : {1, 2}) allow(odd_row_kernel(P, kind)); allow(view_col_kernel(P)); allow(view_c2r_kernel(P)); break;
+    case Family::view:
+        if (P->mirror) { for (int kind : {1, 2}) allow(mirror_row_kernel(P, kind)); allow(mirror_col_kernel(P)); allow(mirror_c2r_kernel(P)); }
+        else { for (int kind : {1, 2}) allow(odd_row_kernel(P, kind)); allow(view_col_kernel(P)); allow(view_c2r_kernel(P)); }
+        break;
     case Family::tuned: allow(tuned_col_kernel(P)); allow(fused_kernel(P)); break;          // (rows: static LDS)
     case Family::mixed_aot: allow(mixed_col_kernel(P)); allow(mixed_c2r_kernel(P)); allow(fused_kernel(P)); break;
     case Family::mixed_jit:           // (a plan-time plan without a row factorization runs the size-generic row kernel)
@@ -555,6 +566,33 @@ static void view_inv(const fftup_plan* P, const Frame& f)
     launch(view_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
 }
 
+// ---- ... with FFTUP_FLAG_MIRROR: reordered row R2C (unphased half spectra) -> column DCT-II through a transform of H points /
+// Z = 2 C[|f|] / chirp-z over the period 2H -> cosine coefficients of two rows / chirp-z over the period 2W -> sharpen
+// (kernels_mirror.hpp; the tables: mirror_tables.hpp)
+static void mirror_rows(const fftup_plan* P, const Frame& f)
+{
+    MirrorRowParams p{};
+    p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
+    p.TK = P->TK; p.NT = P->NT; p.ncols = P->ncols; p.bz = P->bzW;
+    set_in(f, p);
+    launch(mirror_row_kernel(P, f.kind), dim3((P->H + 1) / 2, 3), f.st, p);
+}
+static void mirror_cols(const fftup_plan* P, const Frame& f)
+{
+    MirrorColParams p{};
+    p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.planH = P->planH;
+    p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.kmax = P->vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, P->uH);
+    p.rot = P->rotH;
+    launch(mirror_col_kernel(P), dim3(P->NT, 3), f.st, p);
+}
+static void mirror_inv(const fftup_plan* P, const Frame& f)
+{
+    MirrorC2RParams p{};
+    p.S2 = f.S2; p.R = f.R; p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH;
+    p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.z = czt_plan(P->vx, P->uW); p.rot = P->rotW;
+    launch(mirror_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
+}
+
 // ---- four-step transforms (k_row4_a / k_row4_b): both passes of one
 template <typename C> static void launch_four(const FourKerns<C>& k, const fftup_plan::Four& f, const Row4Params<C>& q, int rows, hipStream_t st)
 {
@@ -764,7 +802,9 @@ static int launch_family(const fftup_plan* P, const Frame& f, Pass pass)
     case Family::dct: return launch_four_passes(P, f, pass, dct_rows, dct_cols, dct_inv);
     case Family::down: return launch_four_passes(P, f, pass, down_rows, down_cols, down_inv);
     case Family::odd: return launch_four_passes(P, f, pass, odd_rows, odd_cols, odd_inv);
-    case Family::view: return launch_four_passes(P, f, pass, odd_rows, view_cols, view_inv);
+    case Family::view:
+        if (P->mirror) return launch_four_passes(P, f, pass, mirror_rows, mirror_cols, mirror_inv);
+        return launch_four_passes(P, f, pass, odd_rows, view_cols, view_inv);
     case Family::tuned: return launch_frame_tuned(P, f, pass);
     case Family::generic: case Family::mixed_aot: case Family::mixed_jit: break;
     }

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "plan.hpp"
+#include "mirror_tables.hpp"
 #include "view_tables.hpp"
 
 using namespace fftup;
@@ -123,7 +124,8 @@ static int view_apply(fftup_plan* P, const fftup_view& v, bool first)
     for (const Ax& x : ax) {
         fftup_viewtab::AxisTables t;
         const bool chirp = first || x.sp != x.sp_old;
-        fftup_viewtab::make_axis(x.N, x.M, x.o, x.sp, x.a->L, t, chirp);
+        if (P->mirror) fftup_viewtab::make_mirror_axis(x.N, x.M, x.o, x.sp, x.a->L, t, chirp);
+        else fftup_viewtab::make_axis(x.N, x.M, x.o, x.sp, x.a->L, t, chirp);
         x.a->kmax = t.kmax;
         HIP_TRY(hipMemcpy(x.a->pre, t.pre.data(), sizeof(float) * t.pre.size(), hipMemcpyHostToDevice));
         if (chirp) {
@@ -132,7 +134,7 @@ static int view_apply(fftup_plan* P, const fftup_view& v, bool first)
         }
     }
     P->vw = v;
-    P->ncols = P->vx.kmax + 1;
+    P->ncols = P->mirror ? fftup_viewtab::mirror_ncols(P->W, P->vx.kmax) : P->vx.kmax + 1;
     P->NT = (P->ncols + P->TK - 1) / P->TK;
     P->cfg.upscale = view_factor(v, P->uW, P->uH);
     P->upsq = const_via_percent_f((double)(P->cfg.upscale * P->cfg.upscale), P->half);
@@ -195,16 +197,21 @@ static int make_tables(fftup_plan* P)
         if (int rc = make_phases(P, &P->phH, P->H, P->uH)) return rc;
     }
     if (P->view) {
-        // tables of the worst case: 2 (N/2) + 1 bins in, M points out, L points of the convolution
+        // tables of the worst case: 2 (N/2) + 1 bins in (mirror plans: 2 N + 1, the doubled period's), M points out, L points of the
+        // convolution
         fftup_plan::ViewAxis* const axes[2] = {&P->vx, &P->vy};
         for (int i = 0; i < 2; i++) {
             fftup_plan::ViewAxis& a = *axes[i];
             a.L = P->viewL[i]; a.planL = make_stage_plan(a.L);
             if (int rc = make_twiddles(P, &a.tw, a.L)) return rc;
-            if (int rc = dev_alloc(P, (void**)&a.pre, sizeof(float2) * (2 * (size_t)(len[i] / 2) + 1))) return rc;
+            if (int rc = dev_alloc(P, (void**)&a.pre, sizeof(float2) * (2 * (size_t)(P->mirror ? len[i] : len[i] / 2) + 1))) return rc;
             if (int rc = dev_alloc(P, (void**)&a.post, sizeof(float2) * len[2 + i])) return rc;
             if (int rc = dev_alloc(P, (void**)&a.bhat, sizeof(float2) * a.L)) return rc;
         }
+    }
+    if (P->mirror) {                                   // exp(i pi k / 2n) of the two input lengths (kernels_mirror.hpp)
+        if (int rc = make_rotations(P, &P->rotW, P->W)) return rc;
+        if (int rc = make_rotations(P, &P->rotH, P->H)) return rc;
     }
     if (P->dct) {
         float2** const rot[4] = {&P->rotW, &P->rotH, &P->rotUW, &P->rotUH};

@@ -107,7 +107,7 @@ struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what li
     uint32_t* png_crc_shift = nullptr; // device table of k_png_crc (created with the first PNG slot)
     bool png_foreign_collector = false; // some thread has collected (fftup_wait_png) a ticket another thread submitted; under q_mu
     float2 *twW = nullptr, *twH = nullptr, *twUW = nullptr, *twUH = nullptr;
-    float2 *rotW = nullptr, *rotH = nullptr, *rotUW = nullptr, *rotUH = nullptr;    // DCT plans: exp(i pi k / 2n), k < n
+    float2 *rotW = nullptr, *rotH = nullptr, *rotUW = nullptr, *rotUH = nullptr;    // DCT plans: exp(i pi k / 2n), k < n (mirror view plans: rotW, rotH)
     uint64_t device_bytes = 0;
     size_t r_bytes = 0;               // bytes of one pre-sharpen image
     uint64_t* d_sum = nullptr;        // fftup_output_checksum accumulator (created on first use)

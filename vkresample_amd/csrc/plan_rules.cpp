@@ -8,6 +8,7 @@
 
 #include <hip/hip_fp16.h>
 
+#include "mirror_tables.hpp"
 #include "view_tables.hpp"
 
 using namespace fftup;
@@ -99,10 +100,15 @@ static int bluestein_col_tk(uint32_t H, uint32_t uH)
         if (lds_length(H, tk) && lds_length(uH, tk)) return tk;
     return 0;
 }
-// column tile width of a view plan: the widest of 8, 4, 2, 1 at which max(H, its Bluestein length, L_y) * TK fits twice; 0: none
-static int view_col_tk(uint32_t H, uint32_t uH)
+// the convolution length of a view plan's axis N -> M: mirror plans convolve over the doubled period
+static uint32_t view_conv_length(uint32_t N, uint32_t M, bool mirror)
 {
-    const uint32_t Ly = fftup_viewtab::conv_length(H, uH);
+    return mirror ? fftup_viewtab::mirror_conv_length(N, M) : fftup_viewtab::conv_length(N, M);
+}
+// column tile width of a view plan: the widest of 8, 4, 2, 1 at which max(H, its Bluestein length, L_y) * TK fits twice; 0: none
+static int view_col_tk(uint32_t H, uint32_t uH, bool mirror)
+{
+    const uint32_t Ly = view_conv_length(H, uH, mirror);
     for (int tk : {8, 4, 2, 1})
         if (lds_length(H, tk) && two_buffers_fit((size_t)std::max(lds_length(H, tk), Ly) * tk)) return tk;
     return 0;
@@ -291,7 +297,10 @@ static int check_view_request(const fftup_config& c, const fftup_view* view, uin
     if (c.precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, "fftup_plan_create_view plans exist for -p 0 and -p 2");
     if (c.flags & FFTUP_FLAG_DCT) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view covers the FFT mode only (no FFTUP_FLAG_DCT)");
     if (W > 8192u) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: rows of at most 8192 points (no non-R2C or four-step path)");
-    if (2 * (uint64_t)(W / 2) + uW > 8192u || fftup_viewtab::conv_length(W, uW) > 8192u)
+    const bool mirror = (c.flags & FFTUP_FLAG_MIRROR) != 0;
+    if (mirror && (2 * (uint64_t)W + uW > 8192u || fftup_viewtab::mirror_conv_length(W, uW) > 8192u))
+        return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_MIRROR: the row convolution length (2,3,5,7-smooth, at least 2 width + out_width) must be at most 8192");
+    if (!mirror && (2 * (uint64_t)(W / 2) + uW > 8192u || fftup_viewtab::conv_length(W, uW) > 8192u))
         return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: the row convolution length (2,3,5,7-smooth, at least 2 (width/2) + out_width) must be at most 8192");
     for (uint32_t n : {W, H}) {
         if (!is_smooth(n) && !(c.flags & FFTUP_FLAG_ANY_SIZE))
@@ -299,7 +308,9 @@ static int check_view_request(const fftup_config& c, const fftup_view* view, uin
         if (!is_smooth(n) && n > BZ_MAX_N)
             return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_ANY_SIZE: " + std::to_string(n) + " has a prime factor above 7 and is longer than 4096");
     }
-    if (2 * (uint64_t)(H / 2) + uH > 16384u || !view_col_tk(H, uH))
+    if (mirror && (2 * (uint64_t)H + uH > 16384u || !view_col_tk(H, uH, true)))
+        return fail(FFTUP_E_UNSUPPORTED_SIZE, "FFTUP_FLAG_MIRROR: the columns must fit the LDS (two buffers of the column convolution length, at least 2 height + out_height, at a tile width of 1)");
+    if (!mirror && (2 * (uint64_t)(H / 2) + uH > 16384u || !view_col_tk(H, uH, false)))
         return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: the columns must fit the LDS (two buffers of the column convolution length at a tile width of 1)");
     return FFTUP_OK;
 }
@@ -382,6 +393,8 @@ int plan_check(const PlanRequest& rq, PlanGeometry& G)
         G.cfg.flags &= ~(uint32_t)FFTUP_FLAG_DOWNSCALE;         // (implied per axis: accepted, changes nothing)
     }
     if (int rc = check_config(G.cfg)) return rc;
+    if ((G.cfg.flags & FFTUP_FLAG_MIRROR) && !G.view)
+        return fail(FFTUP_E_INVALID_ARG, "FFTUP_FLAG_MIRROR is valid on fftup_plan_create_view only (fftup_plan_create and fftup_plan_create_size plans are periodic; FFTUP_FLAG_DCT is their mode without the wrap)");
     const uint32_t W = G.W = G.cfg.width, H = G.H = G.cfg.height;
     const uint32_t uW = G.uW = G.exact ? rq.size[0] : scaled_length(G.cfg.upscale, W);
     const uint32_t uH = G.uH = G.exact ? rq.size[1] : scaled_length(G.cfg.upscale, H);
@@ -401,6 +414,7 @@ int plan_check(const PlanRequest& rq, PlanGeometry& G)
     G.align = G.exact ? rq.align : 0;
     G.down = (G.cfg.flags & FFTUP_FLAG_DOWNSCALE) != 0;
     G.dct = (G.cfg.flags & FFTUP_FLAG_DCT) != 0;
+    G.mirror = G.view && (G.cfg.flags & FFTUP_FLAG_MIRROR);
     // FFTUP_FLAG_ODD_SIZE: odd lengths are valid; `odd`: this plan has one (exact trigonometric resampling, kernels_odd.hpp).  A
     // plan whose four lengths are even is the same plan with or without the flag.
     // (fftup_plan_create_size: always that rule, whatever the parities, FFTUP_FLAG_ODD_SIZE implied)
@@ -451,8 +465,8 @@ static int choose_column_tile(PlanGeometry& G, size_t lds_max)
     // a Bluestein column transform: buffers of L * TK points (bluestein_col_tk: checked before any device access); the
     // column kernel of an odd plan is sized the same way, max(length, L) * TK with L = length for a smooth one
     if (G.view) {
-        G.viewL[0] = fftup_viewtab::conv_length(W, uW); G.viewL[1] = fftup_viewtab::conv_length(H, uH);
-        G.TK = view_col_tk(H, uH);
+        G.viewL[0] = view_conv_length(W, uW, G.mirror); G.viewL[1] = view_conv_length(H, uH, G.mirror);
+        G.TK = view_col_tk(H, uH, G.mirror);
         G.ldsCol = 2 * G.csz * (size_t)lpad_size((int)(std::max(lds_length(H, G.TK), G.viewL[1]) * (uint32_t)G.TK));
         if (G.ldsCol > lds_max) return fail(FFTUP_E_UNSUPPORTED_SIZE, "fftup_plan_create_view: this device's LDS does not hold the column transform");
     }

@@ -89,6 +89,10 @@ struct PlanGeometry {
     // place; ncols = kmax_x + 1 and NT follow the CURRENT view (fftup_plan::vx, vy).  viewL: the smooth convolution length per axis
     bool view = false;
     uint32_t viewL[2] = {0, 0};
+    // ... with FFTUP_FLAG_MIRROR: the view of the frame's half-sample even reflection (kernels_mirror.hpp).  Still Family::view -- the
+    // same passes, buffers and fftup_plan_set_view; the selectors of fftup_launch.hip hand out the mirror kernels.  viewL are the
+    // convolution lengths of the doubled periods (>= 2N + M), ncols = kmax_x + 1 below W/2, else W/2 + 1 (mirror_tables.hpp)
+    bool mirror = false;
     int ncols = 0;                    // spectrum columns kept: W/2 + 1, or W on the non-R2C path
     int pairs_per_strip = 6;
 };

@@ -74,10 +74,11 @@ inline std::complex<long double> expipi(long double x)
 }
 
 // chirp = false: only `pre` (the one table the origin enters) is rebuilt -- a pan at an unchanged span
-inline void make_axis(uint32_t N, uint32_t M, double origin, double span, uint32_t L, AxisTables& t, bool chirp = true)
+// (origin: a double, or -- mirror_tables.hpp -- a double plus one half, exact in long double)
+inline void make_axis(uint32_t N, uint32_t M, long double origin, double span, uint32_t L, AxisTables& t, bool chirp = true)
 {
     const int kmax = kmax_of(N, M, span), K = 2 * kmax + 1;
-    const long double n = (long double)N, s = (long double)span / (long double)M, o = fmodl((long double)origin, n);
+    const long double n = (long double)N, s = (long double)span / (long double)M, o = fmodl(origin, n);
     t.kmax = kmax;
     t.pre.resize(2 * (size_t)K);
     for (int j = 0; j < K; j++) {
