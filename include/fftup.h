@@ -493,6 +493,29 @@ typedef struct fftup_device_image {
 FFTUP_API int fftup_execute_device(fftup_plan* plan, const fftup_device_image* in, const fftup_device_image* out,
                                    uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
 
+/* EXTENSION: a view per frame -- a zoom or pan across a clip, one sub-pixel offset per frame, a viewport that follows a cursor.
+ * fftup_execute_device_views is fftup_execute_device on a VIEW plan (fftup_plan_create_view, with or without FFTUP_FLAG_MIRROR)
+ * with frame i computed with views[i]: everything documented above holds -- formats, in-place rules, containment, ordering,
+ * validation before any launch, no host synchronisation.  Frame i's result is what a plan created with views[i] gives for that
+ * frame, up to the rounding of the chirp tables: they are built ON THE DEVICE, by one kernel (view_tables) enqueued on the frame's
+ * lane ahead of its four kernels, in fp64 with compensated phases (csrc/view_phase.hpp), every entry within one fp32 rounding step
+ * of the host tables fftup_plan_set_view uploads.  Each lane owns a table set (allocated by the first call, freed with the plan);
+ * stream order alone protects it.  A frame whose span on an axis is the one its lane's tables were last built for rebuilds only the
+ * origin's table on that axis (a pan).  The plan's own view is untouched: fftup_plan_set_view, fftup_plan_describe,
+ * fftup_plan_info and later fftup_execute / ring / submit calls stay as they were; fftup_download_presharpen returns the call's
+ * last frame.  The `views` array is read before the call returns.
+ * FFTUP_E_INVALID_ARG, before anything is enqueued, beyond fftup_execute_device's: `views` is null; the plan is not a view plan;
+ * a view breaks a rule of fftup_plan_set_view (fftup_last_error names the frame index and the rule).
+ * Detect the feature by this symbol; fftup_version() and FFTUP_ABI_VERSION are unchanged. */
+FFTUP_API int fftup_execute_device_views(fftup_plan* plan, const fftup_device_image* in, const fftup_device_image* out,
+                                         const fftup_view* views, uint32_t n_frames, void* stream);
+
+/* TEST TAP, in the spirit of fftup_download_presharpen: the tables lane `lane` (< FFTUP_STREAMS) last built for `axis` (0: x, 1: y)
+ * in fftup_execute_device_views.  Interleaved (re, im) floats: pre 2 (2 kmax + 1), post 2 out_length, bhat 2 L (L: the axis'
+ * convolution length, fftup_plan_describe); a null pointer skips that table or kmax.  Waits for the lane's stream first.
+ * FFTUP_E_INVALID_ARG: not a view plan, a lane that has built no tables yet, a bad lane or axis. */
+FFTUP_API int fftup_download_view_tables(fftup_plan* plan, uint32_t lane, uint32_t axis, float* pre, float* post, float* bhat, int32_t* kmax);
+
 /* The device-side siblings of fftup_host_alloc, for hosts without HIP bindings (ctypes, tests): device memory and streams of the
  * runtime this library uses.  fftup_device_alloc: NULL on failure (fftup_last_error).  fftup_device_copy: kind 0 host to device,
  * 1 device to host, 2 device to device; enqueued on `stream` (NULL = the default stream), then waits for `stream`: blocking.

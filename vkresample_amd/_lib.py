@@ -40,6 +40,7 @@ EXPORTS = [
     "fftup_device_pci_bus_id", "fftup_output_checksum", "fftup_png_bound", "fftup_submit_png", "fftup_wait_png",
     "fftup_plan_create_size", "fftup_execute_device", "fftup_device_alloc", "fftup_device_free", "fftup_device_copy",
     "fftup_stream_create", "fftup_stream_destroy", "fftup_plan_create_view", "fftup_plan_set_view",
+    "fftup_execute_device_views", "fftup_download_view_tables",
 ]
 ABI_VERSION = 2
 
@@ -126,6 +127,8 @@ def load():
     lib.fftup_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, sz]
     lib.fftup_output_checksum.argtypes = [vp, u32, C.POINTER(C.c_uint64)]
     lib.fftup_execute_device.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp]
+    lib.fftup_execute_device_views.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(View), u32, vp]
+    lib.fftup_download_view_tables.argtypes = [vp, u32, u32, vp, vp, vp, C.POINTER(C.c_int32)]
     lib.fftup_device_alloc.argtypes = [C.c_int, sz]
     lib.fftup_device_alloc.restype = vp
     lib.fftup_device_free.argtypes = [vp]

@@ -104,6 +104,7 @@ class Upscaler:
         self.width, self.height = width, height
         self.out_width, self.out_height = info.out_width, info.out_height
         self.precision = precision
+        self.flags = flags
         self.ring = max(1, ring)
         self.alg_bytes_per_frame = info.alg_bytes_per_frame
         self.kernel_alg_bytes = list(info.kernel_alg_bytes)
@@ -254,6 +255,34 @@ class Upscaler:
         s = stream.handle if isinstance(stream, Stream) else stream
         _check(self._lib.fftup_execute_device(self._h, a, b, len(ins), s), "fftup_execute_device")
 
+    def execute_device_views(self, inputs, outputs, views, stream=None):
+        """execute_device on a view plan with a view per frame (fftup_execute_device_views): frame i is computed with views[i] =
+        (origin, span), each an (x, y) pair as Upscaler.view takes them -- views_between gives those of a move.  The tables of each
+        view are built on the GPU ahead of its frame: nothing waits, the plan's own view stays what it is."""
+        ins = [inputs] if isinstance(inputs, DeviceImage) else list(inputs)
+        outs = [outputs] if isinstance(outputs, DeviceImage) else list(outputs)
+        vws = list(views)
+        if not len(ins) == len(outs) == len(vws):
+            raise ValueError("execute_device_views: %d inputs, %d outputs, %d views" % (len(ins), len(outs), len(vws)))
+        a = (_lib.DeviceImageDesc * len(ins))(*[i.desc() for i in ins])
+        b = (_lib.DeviceImageDesc * len(outs))(*[o.desc() for o in outs])
+        c = (_lib.View * len(vws))(*[_lib.View(o[0], o[1], sp[0], sp[1]) for (o, sp) in vws])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_execute_device_views(self._h, a, b, c, len(ins), s), "fftup_execute_device_views")
+
+    def download_view_tables(self, lane, axis):
+        """The chirp tables lane `lane` last built for axis 0 (x) or 1 (y) in execute_device_views (fftup_download_view_tables, a
+        test tap): (kmax, pre, post, bhat), complex64 arrays of 2 kmax + 1, out length and L points."""
+        n, m = ((self.width, self.out_width), (self.height, self.out_height))[axis] if axis in (0, 1) else (2, 2)
+        need = (2 * n if self.flags & _lib.FLAG_MIRROR else 2 * (n // 2)) + m
+        L = next(q for q in range(need, 4 * need + 8) if _smooth(q))
+        pre = np.zeros(need - m + 1, np.complex64)
+        post, bhat = np.zeros(m, np.complex64), np.zeros(L, np.complex64)
+        kmax = C.c_int32()
+        _check(self._lib.fftup_download_view_tables(self._h, lane, axis, pre.ctypes.data, post.ctypes.data, bhat.ctypes.data, C.byref(kmax)),
+               "fftup_download_view_tables")
+        return kmax.value, pre[:2 * kmax.value + 1], post, bhat
+
 
 class DeviceImage:
     """One image in device memory (fftup_device_image): `ptr` an address of the plan's device, `format` FMT_RGB8 or FMT_PLANAR,
@@ -371,6 +400,30 @@ def view_of_rect(x0, y0, w, h, out_width, out_height):
     """(origin, span) of Upscaler.view for the rectangle [x0, x0 + w) x [y0, y0 + h) in pixel-EDGE coordinates (pixel n covers
     [n, n + 1)), pixel centres aligned: per axis origin = x0 + w / (2 M) - 1/2, span = w."""
     return ((x0 + w / (2.0 * out_width) - 0.5, y0 + h / (2.0 * out_height) - 0.5), (float(w), float(h)))
+
+
+def views_between(v0, v1, n):
+    """The n views of a move from v0 to v1 (each (origin, span), (x, y) pairs), for Upscaler.execute_device_views.  Frame k, t = k / (n - 1):
+    per axis the origin is linear in t, (1 - t) o0 + t o1, the span geometric, span0 (span1 / span0) ** t -- a zoom at a constant
+    rate.  The first view is v0 and the last v1, exactly; n = 1 gives [v0]."""
+    def as_view(v):
+        return ((float(v[0][0]), float(v[0][1])), (float(v[1][0]), float(v[1][1])))
+    v0, v1 = as_view(v0), as_view(v1)
+    out = []
+    for k in range(n):
+        if k == 0 or k == n - 1:
+            out.append(v0 if k == 0 else v1)
+            continue
+        t = k / (n - 1)
+        out.append((tuple((1.0 - t) * a + t * b for a, b in zip(v0[0], v1[0])), tuple(a * (b / a) ** t for a, b in zip(v0[1], v1[1]))))
+    return out
+
+
+def _smooth(n):
+    for p in (2, 3, 5, 7):
+        while n % p == 0:
+            n //= p
+    return n == 1
 
 
 def upscale_image(rgb, upscale=2.0, precision=0, sharpen=0.2, num_iter=1, device=0, flags=0):

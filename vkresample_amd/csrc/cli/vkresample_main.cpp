@@ -24,6 +24,8 @@
 //   -view ox,oy,sx,sy  with -size: fftup_plan_create_view -- the output shows the rectangle of the frame that starts at input position
 //                 (ox, oy) and spans (sx, sy) input pixels: zoom, sub-pixel pan, any real ratio (the frame is periodic)
 //   -mirror       with -size and -view: FFTUP_FLAG_MIRROR -- the frame is continued by its reflection instead: no wrap at the borders
+//   -viewto ox,oy,sx,sy -frames K  with -size and -view: one image, K frames whose view moves from -view to -viewto, in ONE
+//                 fftup_execute_device_views call on device buffers; K files, -o NAME.png -> NAME_0001.png ...
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -64,7 +66,72 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     uint32_t align = FFTUP_ALIGN_CORNER;     // -centres
     bool hasView = false;                    // -view ox,oy,sx,sy (with -size)
     fftup_view view{};
+    uint32_t frames = 0;                     // -viewto ox,oy,sx,sy -frames K: a clip of K views from `view` to `viewTo` (0: none)
+    fftup_view viewTo{};
 };
+
+// frame k of the K views of a move from a to b, t = k / (K - 1): per axis the origin linear in t, the span geometric; the ends exact
+// (vkresample_amd.views_between is the same formula)
+static fftup_view view_between(const fftup_view& a, const fftup_view& b, uint32_t k, uint32_t K)
+{
+    if (k == 0) return a;
+    if (k == K - 1) return b;
+    const double t = (double)k / (double)(K - 1);
+    fftup_view v;
+    v.origin_x = (1.0 - t) * a.origin_x + t * b.origin_x;
+    v.origin_y = (1.0 - t) * a.origin_y + t * b.origin_y;
+    v.span_x = a.span_x * std::pow(b.span_x / a.span_x, t);
+    v.span_y = a.span_y * std::pow(b.span_y / a.span_y, t);
+    return v;
+}
+
+// -viewto: ONE image, K views, K files -- the whole clip is one fftup_execute_device_views call on device buffers (the image once,
+// K output images); the tables of every view are built on the GPU ahead of its frame.  `-o NAME.png` gives NAME_0001.png ...
+static int run_view_clip(const ResampleConfiguration& config, fftup_plan* plan, const std::vector<uint8_t>& rgb, int width, int height, uint32_t uW, uint32_t uH)
+{
+    const uint32_t K = config.frames;
+    const size_t inBytes = (size_t)width * height * 3, outBytes = (size_t)uW * uH * 3;
+    std::vector<fftup_view> views(K);
+    for (uint32_t k = 0; k < K; k++) {
+        views[k] = view_between(config.view, config.viewTo, k, K);
+        printf("view %u: %.17g %.17g %.17g %.17g\n", k, views[k].origin_x, views[k].origin_y, views[k].span_x, views[k].span_y);
+    }
+    void* din = fftup_device_alloc(config.device_id, inBytes);
+    void* dout = fftup_device_alloc(config.device_id, outBytes * K);
+    int res = (din && dout) ? FFTUP_OK : FFTUP_E_OUT_OF_MEMORY;
+    if (res == FFTUP_OK) res = fftup_device_copy(din, rgb.data(), inBytes, 0, nullptr);
+    if (res == FFTUP_OK) {
+        std::vector<fftup_device_image> in(K), out(K);
+        for (uint32_t k = 0; k < K; k++) {
+            in[k] = {din, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            out[k] = {(uint8_t*)dout + outBytes * k, FFTUP_FMT_RGB8, (size_t)uW * 3, 0};
+        }
+        res = fftup_execute_device_views(plan, in.data(), out.data(), views.data(), K, nullptr);
+    }
+    std::vector<uint8_t> host(outBytes * K);
+    if (res == FFTUP_OK) res = fftup_device_copy(host.data(), dout, outBytes * K, 1, nullptr);   // (ordered behind the clip, blocking)
+    fftup_device_free(din);
+    fftup_device_free(dout);
+    if (res != FFTUP_OK) {
+        printf("Upscale failed: %s (%s)\n", fftup_strerror(res), fftup_last_error());
+        return res;
+    }
+    char base[900];
+    if (config.png_output_name) snprintf(base, sizeof base, "%s", config.png_output_name);
+    else snprintf(base, sizeof base, "%d_%d_upscaled.png", width, (int)uW);
+    std::string stem = base, ext;
+    const size_t dot = stem.find_last_of('.'), slash = stem.find_last_of('/');
+    if (dot != std::string::npos && (slash == std::string::npos || dot > slash)) { ext = stem.substr(dot); stem.resize(dot); }
+    for (uint32_t k = 0; k < K; k++) {
+        char num[16];
+        snprintf(num, sizeof num, "_%04u", k + 1);
+        const std::string name = stem + num + ext;
+        std::string err;
+        if (!pngio::write_rgb8(name.c_str(), host.data() + outBytes * k, (int)uW, (int)uH, (size_t)uW * 3, err))
+            printf("Could not write %s: %s\n", name.c_str(), err.c_str());
+    }
+    return FFTUP_OK;
+}
 
 // fftup_plan_create, fftup_plan_create_size under -size, fftup_plan_create_view under -size with -view
 static int create_plan(const ResampleConfiguration& config, fftup_plan** plan, const fftup_config& cfg)
@@ -290,6 +357,12 @@ static int launchResample(ResampleConfiguration config)                      // 
         printf("Thread %d finished. Device name: %s API:HIP\n", config.threadId, info.device_name);   // VR:1773
         return FFTUP_OK;
     }
+    if (config.frames) {                                                       // -viewto: single image mode only (main checks)
+        res = run_view_clip(config, plan, png_input, width, height, uW, uH);
+        fftup_plan_destroy(plan);
+        if (res == FFTUP_OK) printf("Thread %d finished. Device name: %s API:HIP\n", config.threadId, info.device_name);
+        return res;
+    }
     for (int f = 0; config.fileUpload ? fileAt(f) > 0 : f < 1; f++) {
         if (f > 0) {
             snprintf(fileName, sizeof fileName, "%s/%06d.png", config.ifolder_prefix, fileAt(f));
@@ -376,6 +449,7 @@ int main(int argc, char* argv[])
         printf("	-centres: with -size: align the pixel centres, as other resizers do (default: output pixel 0 on input pixel 0)\n");
         printf("	-view OX,OY,SX,SY: with -size: show the rectangle of the image that starts at position (OX, OY) and spans SX x SY input pixels, e.g. -size 1920x1080 -view 480,270,960,540 on 1920x1080: a 2x zoom about the centre; any real numbers (sub-pixel pan, any ratio; the image is periodic; a step SX/W outside [1/64, 8] is refused; not with -centres)\n");
         printf("	-mirror: with -size and -view: continue the image by its reflection instead of periodically: no wrap-around at the borders, e.g. -size 1920x1080 -view -0.144,-0.144,1366,768 -mirror -anysize on 1366x768 (-p 0 and -p 2, not with -dct)\n");
+        printf("	-viewto OX,OY,SX,SY -frames K: with -size and -view, single image mode: a clip of K frames (2 to 9999) whose view moves from -view to -viewto (position linear, span geometric); -o NAME.png gives NAME_0001.png ...; the views are printed, one 'view k: ox oy sx sy' line each\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -448,6 +522,23 @@ int main(int argc, char* argv[])
     if (findFlag(B, E, "-mirror")) {
         if (!config.hasView) { printf("-mirror needs a view given with -size and -view\n"); return 1; }
         config.flags |= FFTUP_FLAG_MIRROR;
+    }
+    if (findFlag(B, E, "-viewto") || findFlag(B, E, "-frames")) {
+        char* w = getFlagValue(B, E, "-viewto");
+        char* k = getFlagValue(B, E, "-frames");
+        char tail = 0;
+        if (!findFlag(B, E, "-viewto")) { printf("-frames needs a last view given with -viewto\n"); return 1; }
+        if (!config.hasView) { printf("-viewto needs a first view given with -size and -view\n"); return 1; }
+        if (!findFlag(B, E, "-frames")) { printf("-viewto needs a number of frames given with -frames\n"); return 1; }
+        if (findFlag(B, E, "-ifolder")) { printf("-viewto works on one image (-i): it cannot be combined with -ifolder\n"); return 1; }
+        if (!w || sscanf(w, "%lf,%lf,%lf,%lf%c", &config.viewTo.origin_x, &config.viewTo.origin_y, &config.viewTo.span_x, &config.viewTo.span_y, &tail) != 4) {
+            printf("No proper view is selected with -viewto flag (OX,OY,SX,SY, e.g. 480,270,960,540)\n");
+            return 1;
+        }
+        if (!k || sscanf(k, "%u%c", &config.frames, &tail) != 1 || config.frames < 2 || config.frames > 9999) {
+            printf("No proper number of frames is selected with -frames flag (2 to 9999)\n");
+            return 1;
+        }
     }
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");

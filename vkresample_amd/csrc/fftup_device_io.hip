@@ -86,11 +86,8 @@ int ensure_events(fftup_plan* P)
     return FFTUP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, uint32_t n_frames, void* stream)
+// fftup_execute_device, and with `views` fftup_execute_device_views: frame i computed with views[i] instead of the plan's view
+int execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views, uint32_t n_frames, void* stream)
 {
     if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
     if (!in || !out) return fail(FFTUP_E_INVALID_ARG, "null image array");
@@ -100,12 +97,14 @@ int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftu
     for (uint32_t i = 0; i < n_frames; i++) {
         int rc = check_image(P, in[i], "in", i, P->W, P->H, false);
         if (!rc) rc = check_image(P, out[i], "out", i, P->uW, P->uH, true);
+        if (!rc && views) rc = check_view(("fftup_execute_device_views: views[" + std::to_string(i) + "]").c_str(), &views[i], P->uW, P->uH);
         if (rc) return rc;
     }
     int rc = ensure_events(P);
     if (rc) return rc;
     // consecutive frames alternate on the plan's lanes, as in fftup_execute_ring
     const int nl = (int)std::min<uint32_t>((uint32_t)P->nlanes, n_frames);
+    if (views && (rc = view_frames_prepare(P, nl))) return rc;          // (the lanes' table sets, on first use)
     const size_t esz = P->esz, out_bytes = (size_t)3 * P->uW * P->uH * (P->u8out ? 1 : esz);
     for (uint32_t i = 0; i < n_frames; i++) {                 // the staging of the layouts that cannot run in place, on first use
         const int l = (int)(i % (uint32_t)nl);
@@ -131,7 +130,7 @@ int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftu
                                   P->W * esz, P->H, 3, 1, st);             // (the source is not element aligned: bytes)
             io.in = stage; io.kind = 1; io.in_row = (long)P->W; io.in_plane = (long)P->in_plane_stride;
         }
-        const FrameRun r{l, 0, ro.in_place ? dst.data : P->dio.scratch_out[l], &io};
+        const FrameRun r{l, 0, ro.in_place ? dst.data : P->dio.scratch_out[l], &io, Pass::all, views ? &views[i] : nullptr};
         if ((rc = launch_frame(P, r))) break;
         if (!ro.in_place) {
             if (dst.format == FFTUP_FMT_PLANAR)
@@ -149,6 +148,43 @@ int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftu
     rc = lanes_join(P, 0, nl, {cs, P->stream}, rc);
     if (!rc) P->dev_executed = true;
     return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, uint32_t n_frames, void* stream)
+{
+    return execute_device(P, in, out, nullptr, n_frames, stream);
+}
+
+int fftup_execute_device_views(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views,
+                               uint32_t n_frames, void* stream)
+{
+    if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
+    if (!views) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views: views is null");
+    if (!P->view) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views: not a view plan (fftup_plan_create_view makes one)");
+    return execute_device(P, in, out, views, n_frames, stream);
+}
+
+// the parity tests' tap: the tables lane `lane` last built for axis 0 (x) or 1 (y)
+int fftup_download_view_tables(fftup_plan* P, uint32_t lane, uint32_t axis, float* pre, float* post, float* bhat, int32_t* kmax)
+{
+    if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
+    if (!P->view) return fail(FFTUP_E_INVALID_ARG, "fftup_download_view_tables: not a view plan (fftup_plan_create_view makes one)");
+    if (axis > 1) return fail(FFTUP_E_INVALID_ARG, "fftup_download_view_tables: axis must be 0 (x) or 1 (y)");
+    if (lane >= (uint32_t)P->nlanes) return fail(FFTUP_E_INVALID_ARG, "fftup_download_view_tables: lane out of range");
+    if (lane >= P->vtabs.size() || !P->vtabs[lane].built) return fail(FFTUP_E_INVALID_ARG, "fftup_download_view_tables: this lane has built no tables yet (fftup_execute_device_views does)");
+    HIP_TRY(hipSetDevice(P->device));
+    HIP_TRY(hipStreamSynchronize(P->lanes[lane].stream));
+    const fftup_plan::ViewTabs& t = P->vtabs[lane];
+    const size_t M = axis ? P->uH : P->uW, L = axis ? P->vy.L : P->vx.L, K = 2 * (size_t)t.kmax[axis] + 1;
+    if (pre) HIP_TRY(hipMemcpy(pre, t.pre[axis], sizeof(float2) * K, hipMemcpyDeviceToHost));
+    if (post) HIP_TRY(hipMemcpy(post, t.post[axis], sizeof(float2) * M, hipMemcpyDeviceToHost));
+    if (bhat) HIP_TRY(hipMemcpy(bhat, t.bhat[axis], sizeof(float2) * L, hipMemcpyDeviceToHost));
+    if (kmax) *kmax = t.kmax[axis];
+    return FFTUP_OK;
 }
 
 void* fftup_device_alloc(int device, size_t bytes)

@@ -29,7 +29,9 @@
 #include "kernels_odd.hpp"
 #include "kernels_view.hpp"
 #include "kernels_mirror.hpp"
+#include "kernels_view_tables.hpp"
 #include "kernels_device_io.hpp"
+#include "mirror_tables.hpp"
 
 using namespace fftup;
 using Family = fftup_plan::Family;
@@ -46,11 +48,16 @@ size_t kernels_tuned_col_lds(uint32_t H) { return sizeof(float2) * (size_t)lswz_
 
 // One frame as the frame functions see it, a FrameRun resolved once by launch_frame: the lane's stream and buffers, where the first kernel
 // reads (a ring slot or the caller's DeviceInput; kind 1 planes, 2 8-bit RGB, 0 nothing uploaded) and where the last one writes
-struct Frame { hipStream_t st; float2 *S1, *S2; void *R, *T4; const void* in; long in_row, in_plane; int kind; void* out; };
+// -- and what follows the frame's view: the spectrum columns kept (ncols, NT), the sharpen constant upsq, and for view plans kmax and
+// the chirp tables per axis.  Filled from the plan; a FrameRun with a view of its own replaces them (frame_view below)
+struct ViewTables { int kmax; const float2 *pre, *post, *bhat; };
+struct Frame { hipStream_t st; float2 *S1, *S2; void *R, *T4; const void* in; long in_row, in_plane; int kind; void* out;
+               int ncols, NT; float upsq; ViewTables vx, vy; };
 static Frame resolve(const fftup_plan* P, const FrameRun& r)
 {
     const fftup_plan::Lane& l = P->lanes[r.lane];
-    Frame f{l.stream, l.S1, l.S2, l.R, l.T4, P->in_planar[r.in_slot], (long)P->W, (long)P->in_plane_stride, P->in_kind[r.in_slot], r.out};
+    Frame f{l.stream, l.S1, l.S2, l.R, l.T4, P->in_planar[r.in_slot], (long)P->W, (long)P->in_plane_stride, P->in_kind[r.in_slot], r.out,
+            P->ncols, P->NT, P->upsq, {P->vx.kmax, P->vx.pre, P->vx.post, P->vx.bhat}, {P->vy.kmax, P->vy.pre, P->vy.post, P->vy.bhat}};
     if (r.in) { f.in = r.in->in; f.in_row = r.in->in_row; f.in_plane = r.in->kind == 2 ? 0 : r.in->in_plane; f.kind = r.in->kind; }
     else if (f.kind == 2) { f.in = P->in_u8[r.in_slot]; f.in_row = 3l * P->W; f.in_plane = 0; }
     return f;
@@ -418,7 +425,7 @@ static bool fast_sharpen_ok(const fftup_plan* P) { return !P->dbl && P->uW % 256
 static void launch_sharpen_fast(const fftup_plan* P, const Frame& f)
 {
     SharpenTParams p{};
-    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = f.upsq; p.coef = P->coef;
     dim3 grid(P->uW / 256, P->uH / 16, 3), block(64, 4);
     if (P->half) hipLaunchKernelGGL((k_sharpen_t<true, 4>), grid, block, 0, f.st, p);
     else hipLaunchKernelGGL((k_sharpen_t<false, 4>), grid, block, 0, f.st, p);
@@ -429,7 +436,7 @@ static void launch_sharpen(const fftup_plan* P, const Frame& f)
 {
     if (fast_sharpen_ok(P)) { launch_sharpen_fast(P, f); return; }
     SharpenParams p{};
-    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = P->upsq; p.coef = P->coef;
+    p.R = f.R; p.out = f.out; p.uW = (int)P->uW; p.uH = (int)P->uH; p.upsq = f.upsq; p.coef = P->coef;
     dim3 grid((P->uW + 1023) / 1024, P->uH, 3), block(256);      // (four pixels per thread; a width of 2 gave an empty grid until round 5)
     if (P->half) hipLaunchKernelGGL(k_sharpen<true>, grid, block, 0, f.st, p);
     else hipLaunchKernelGGL(k_sharpen<false>, grid, block, 0, f.st, p);
@@ -519,8 +526,8 @@ static void odd_rows(const fftup_plan* P, const Frame& f)
     const bool view = P->family == Family::view;
     OddRowParams p{};
     p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
-    p.TK = P->TK; p.NT = P->NT; p.bz = P->bzW;
-    p.kmax = view ? P->vx.kmax : (int)std::min(P->W, P->uW) / 2;
+    p.TK = P->TK; p.NT = f.NT; p.bz = P->bzW;
+    p.kmax = view ? f.vx.kmax : (int)std::min(P->W, P->uW) / 2;
     p.fold = (!view && P->uW < P->W && !(P->uW & 1)) ? 1 : 0;
     p.ph = view ? nullptr : P->phW;
     set_in(f, p);
@@ -545,24 +552,25 @@ static void odd_inv(const fftup_plan* P, const Frame& f)
 
 // ---- fftup_plan_create_view: the odd-size plans' row R2C -> column forward / signed bins / chirp-z to uH points -> two spectrum
 // rows / chirp-z to uW points -> sharpen (kernels_view.hpp)
-static CztPlan czt_plan(const fftup_plan::ViewAxis& a, uint32_t M)
+// (the length, its radix list and roots are the plan's; kmax and the three tables the frame's)
+static CztPlan czt_plan(const fftup_plan::ViewAxis& a, const ViewTables& t, uint32_t M)
 {
     CztPlan z{};
-    z.L = (int32_t)a.L; z.K = 2 * a.kmax + 1; z.M = (int32_t)M; z.plan = a.planL; z.tw = a.tw; z.pre = a.pre; z.post = a.post; z.bhat = a.bhat;
+    z.L = (int32_t)a.L; z.K = 2 * t.kmax + 1; z.M = (int32_t)M; z.plan = a.planL; z.tw = a.tw; z.pre = t.pre; z.post = t.post; z.bhat = t.bhat;
     return z;
 }
 static void view_cols(const fftup_plan* P, const Frame& f)
 {
     ViewColParams p{};
     p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.planH = P->planH;
-    p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.kmax = P->vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, P->uH);
-    launch(view_col_kernel(P), dim3(P->NT, 3), f.st, p);
+    p.H = (int)P->H; p.uH = (int)P->uH; p.NT = f.NT; p.ncols = f.ncols; p.kmax = f.vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, f.vy, P->uH);
+    launch(view_col_kernel(P), dim3(f.NT, 3), f.st, p);
 }
 static void view_inv(const fftup_plan* P, const Frame& f)
 {
     ViewC2RParams p{};
     p.S2 = f.S2; p.R = f.R; p.uW = (int)P->uW; p.uH = (int)P->uH;
-    p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.z = czt_plan(P->vx, P->uW);
+    p.TK = P->TK; p.NT = f.NT; p.kmax = f.vx.kmax; p.z = czt_plan(P->vx, f.vx, P->uW);
     launch(view_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
 }
 
@@ -573,7 +581,7 @@ static void mirror_rows(const fftup_plan* P, const Frame& f)
 {
     MirrorRowParams p{};
     p.S1 = f.S1; p.tw = P->twW; p.plan = P->planW; p.W = (int)P->W; p.H = (int)P->H;
-    p.TK = P->TK; p.NT = P->NT; p.ncols = P->ncols; p.bz = P->bzW;
+    p.TK = P->TK; p.NT = f.NT; p.ncols = f.ncols; p.bz = P->bzW;
     set_in(f, p);
     launch(mirror_row_kernel(P, f.kind), dim3((P->H + 1) / 2, 3), f.st, p);
 }
@@ -581,15 +589,15 @@ static void mirror_cols(const fftup_plan* P, const Frame& f)
 {
     MirrorColParams p{};
     p.S1 = f.S1; p.S2 = f.S2; p.twH = P->twH; p.planH = P->planH;
-    p.H = (int)P->H; p.uH = (int)P->uH; p.NT = P->NT; p.ncols = P->ncols; p.kmax = P->vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, P->uH);
+    p.H = (int)P->H; p.uH = (int)P->uH; p.NT = f.NT; p.ncols = f.ncols; p.kmax = f.vy.kmax; p.bzH = P->bzH; p.z = czt_plan(P->vy, f.vy, P->uH);
     p.rot = P->rotH;
-    launch(mirror_col_kernel(P), dim3(P->NT, 3), f.st, p);
+    launch(mirror_col_kernel(P), dim3(f.NT, 3), f.st, p);
 }
 static void mirror_inv(const fftup_plan* P, const Frame& f)
 {
     MirrorC2RParams p{};
     p.S2 = f.S2; p.R = f.R; p.W = (int)P->W; p.uW = (int)P->uW; p.uH = (int)P->uH;
-    p.TK = P->TK; p.NT = P->NT; p.kmax = P->vx.kmax; p.z = czt_plan(P->vx, P->uW); p.rot = P->rotW;
+    p.TK = P->TK; p.NT = f.NT; p.kmax = f.vx.kmax; p.z = czt_plan(P->vx, f.vx, P->uW); p.rot = P->rotW;
     launch(mirror_c2r_kernel(P), dim3((P->uH + 1) / 2, 3), f.st, p);
 }
 
@@ -810,12 +818,76 @@ static int launch_family(const fftup_plan* P, const Frame& f, Pass pass)
     }
     return launch_frame_generic(P, f, pass);
 }
+// ---- a frame with a view of its own (fftup_execute_device_views): what view_apply derives on the host for the plan's view, here
+// for this frame -- kmax per axis as kmax_of / mirror_kmax_of, the columns kept, the sharpen constant of its spans -- and the
+// tables from k_view_tables, enqueued on the lane's stream ahead of the frame's kernels into the lane's own set (view_frames_prepare
+// made it).  An axis whose span is the one the lane's chirp tables were built for rebuilds `pre` alone.  No event, no copy, no
+// host synchronisation: the lane's next frame rebuilds the tables behind this frame's last reader.
+static Kern<ViewTabParams> view_tables_kernel(const fftup_plan* P)
+{
+    return kern(k_view_tables, VT_THREADS, sizeof(double2) * (size_t)lpad_size((int)std::max(P->vx.L, P->vy.L)));
+}
+int kernels_allow_view_tables(const fftup_plan* P)
+{
+    for (uint32_t L : {P->vx.L, P->vy.L}) {                   // (every L a view plan accepts passes: its two float2 buffers fit the LDS)
+        if (L > (uint32_t)VT_MAX_L) return fail(FFTUP_E_UNSUPPORTED_SIZE, "k_view_tables: convolution length above " + std::to_string(VT_MAX_L));
+        const StagePlan sp = make_stage_plan(L);
+        for (int s = 0; s < sp.nstages; s++)
+            if (!stage_fits_inplace((int)L, sp.radix[s], VT_THREADS, VT_PT)) return fail(FFTUP_E_UNSUPPORTED_SIZE, "k_view_tables: a stage does not fit its registers");
+    }
+    AllowLds allow;
+    allow(view_tables_kernel(P));
+    if (allow.err != hipSuccess) return fail(FFTUP_E_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(allow.err));
+    return FFTUP_OK;
+}
+static void frame_view(fftup_plan* P, int lane, const fftup_view& v, Frame& f)
+{
+    fftup_plan::ViewTabs& t = P->vtabs[lane];
+    struct Ax { const fftup_plan::ViewAxis* a; uint32_t N, M; double o, sp; ViewTables* out; };
+    const Ax ax[2] = {{&P->vx, P->W, P->uW, v.origin_x, v.span_x, &f.vx}, {&P->vy, P->H, P->uH, v.origin_y, v.span_y, &f.vy}};
+    ViewTabParams p{};
+    for (int i = 0; i < 2; i++) {
+        const Ax& x = ax[i];
+        ViewTabAxis& q = p.ax[i];
+        q.n = (int32_t)(P->mirror ? 2 * x.N : x.N); q.M = (int32_t)x.M; q.L = (int32_t)x.a->L;
+        q.kmax = P->mirror ? fftup_viewtab::mirror_kmax_of(x.N, x.M, x.sp) : fftup_viewtab::kmax_of(x.N, x.M, x.sp);
+        q.chirp = t.span[i] != x.sp;
+        const fftup_viewphase::Pair o = fftup_viewphase::origin_of(x.o, (double)q.n, P->mirror);
+        q.o_hi = o.hi; q.o_lo = o.lo; q.span = x.sp; q.plan = x.a->planL; q.tw = P->vroots[i];
+        q.pre = t.pre[i]; q.post = t.post[i]; q.bhat = t.bhat[i];
+        t.span[i] = x.sp; t.kmax[i] = q.kmax;
+        *x.out = {q.kmax, q.pre, q.post, q.bhat};
+    }
+    t.built = true;
+    f.ncols = P->mirror ? fftup_viewtab::mirror_ncols(P->W, f.vx.kmax) : f.vx.kmax + 1;
+    f.NT = (f.ncols + P->TK - 1) / P->TK;
+    const float u = view_factor(v, P->uW, P->uH);
+    f.upsq = const_via_percent_f((double)(u * u), P->half);
+    // (test builds, FFTUP_EXPERIMENT view_tables_time=1: the kernel alone between the plan's pair of timing events, reported on
+    // stderr for tools/view_frames_time.py -- this waits for the lane, which the call otherwise never does)
+    const char* ex = fftup_jit::experiment("view_tables_time");
+    const bool timed = ex && atoi(ex) != 0;
+    if (timed) (void)hipEventRecord(P->ev0, f.st);
+    launch(view_tables_kernel(P), dim3(2), f.st, p);
+    if (timed) {
+        float ms = 0;
+        (void)hipEventRecord(P->ev1, f.st);
+        if (hipEventSynchronize(P->ev1) == hipSuccess && hipEventElapsedTime(&ms, P->ev0, P->ev1) == hipSuccess)
+            fprintf(stderr, "fftup: k_view_tables %.3f us (chirp tables rebuilt: x %d, y %d)\n", (double)ms * 1e3, p.ax[0].chirp, p.ax[1].chirp);
+    }
+}
+
 int launch_frame(fftup_plan* P, const FrameRun& r)
 {
-    const Frame f = resolve(P, r);
+    Frame f = resolve(P, r);
     const bool tap = r.pass == Pass::presharpen_tap;
     if (f.kind == 0 && !tap) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (the tap reads spectra only)
+    if (r.view) {
+        if (P->family != Family::view || (size_t)r.lane >= P->vtabs.size() || !P->vtabs[r.lane].pre[0]) return fail(FFTUP_E_INVALID_ARG, "a frame with a view of its own: not a view plan, or its lane has no tables");
+        frame_view(P, r.lane, *r.view, f);
+    }
     const int rc = launch_family(P, f, r.pass);
+    if (rc && r.view) P->vtabs[r.lane].span[0] = P->vtabs[r.lane].span[1] = 0;      // (a failed launch: the lane's chirp tables are nobody's)
     // what the frame left: its inverse rows have run, so the tap reads this lane's spectra, or its R unless the fused kernel ran instead
     if (tap || runs(r.pass, Pass::inverse)) { P->last_lane = r.lane; P->R_valid = !(P->fused && !tap); }
     return rc;

@@ -142,6 +142,34 @@ static int view_apply(fftup_plan* P, const fftup_view& v, bool first)
 }
 
 
+// fftup_execute_device_views, on first use (like the device-I/O staging; the plan frees them): for the lanes [0, nl) a table set
+// each with the sizes make_tables gives the plan's own, which k_view_tables fills per frame; per axis the L-th roots in double
+// -- the table make_twiddles gives a -p 1 plan -- uploaded once; the kernel's LDS attribute
+int view_frames_prepare(fftup_plan* P, int nl)
+{
+    if (P->vtabs.empty()) P->vtabs.resize(P->nlanes);
+    const uint32_t len[4] = {P->W, P->H, P->uW, P->uH};
+    const fftup_plan::ViewAxis* const axes[2] = {&P->vx, &P->vy};
+    if (!P->vroots[0]) {
+        if (int rc = kernels_allow_view_tables(P)) return rc;
+        for (int i = 0; i < 2; i++) {
+            float2* d = nullptr;
+            if (int rc = upload_table(P, &d, roots<double2>(axes[i]->L))) return rc;
+            P->vroots[i] = (double2*)d;
+        }
+    }
+    for (int l = 0; l < nl; l++) {
+        fftup_plan::ViewTabs& t = P->vtabs[l];
+        for (int i = 0; i < 2 && !t.bhat[1]; i++) {
+            if (int rc = dev_alloc(P, (void**)&t.pre[i], sizeof(float2) * (2 * (size_t)(P->mirror ? len[i] : len[i] / 2) + 1))) return rc;
+            if (int rc = dev_alloc(P, (void**)&t.post[i], sizeof(float2) * len[2 + i])) return rc;
+            if (int rc = dev_alloc(P, (void**)&t.bhat[i], sizeof(float2) * axes[i]->L)) return rc;
+        }
+    }
+    return FFTUP_OK;
+}
+
+
 static void tune_fused(fftup_plan* P);
 static bool jit_tune_enabled()
 {

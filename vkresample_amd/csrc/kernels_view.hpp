@@ -9,7 +9,7 @@
 // -- a convolution, run as a cyclic one of a 2,3,5,7-smooth length L >= K + M - 1 through the Stockham stages that exist:
 //     a[j] = Z_j pre[j] (zero up to L),  A = FFT_L(a),  A[k] *= bhat[k],  r = IFFT_L(A),  y[m] = r[m] post[m].
 // The tables come from the host (view_tables.hpp: long double phases, reduced before the multiplication by pi, rounded once to
-// fp32); post carries the normalisation (1/N) (span/M) of the pre-sharpen image R = y span_x span_y / (uW uH).
+// fp32) or, for a frame that brings its own view, from k_view_tables (kernels_view_tables.hpp); post carries the normalisation (1/N) (span/M) of the pre-sharpen image R = y span_x span_y / (uW uH).
 //
 // The forward transforms of these plans run with exp(+2 pi i nk / N) (fft_any<+1>), as in kernels_odd.hpp: bin k of the kernels holds
 // the frequency -k.  The gathers below read Z_j = X[f] from kernel bin -f = kmax - j.

@@ -8,7 +8,7 @@
 //   fftup_execute.hip  upload / execute / download (performVulkanUpscale, VkResample.cpp:1249-1279, and the transfers)
 //   fftup_queue.hip    host-streamed frames: fftup_submit_rgb8 / fftup_wait / fftup_drain
 //   fftup_png.hip      the device-side PNG encoder's host side
-//   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device and the device / stream helpers
+//   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views and the device / stream helpers
 //   jit.cpp            the plan-time compiler
 #pragma once
 #include <hip/hip_runtime.h>
@@ -72,6 +72,13 @@ struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what li
     fftup_view vw{};
     struct ViewAxis { int kmax = 0; uint32_t L = 0; StagePlan planL{}; float2 *tw = nullptr, *pre = nullptr, *post = nullptr, *bhat = nullptr; };
     ViewAxis vx, vy;
+    // fftup_execute_device_views, created by the first call: per lane a table set of its own (the sizes of vx / vy's), which
+    // k_view_tables fills on the lane's stream ahead of each frame; span: the span whose post / bhat the lane holds on that axis
+    // (0: none yet), kmax: of the tables last built; vroots: the L-th roots in double per axis, shared by the lanes
+    struct ViewTabs { float2 *pre[2] = {nullptr, nullptr}, *post[2] = {nullptr, nullptr}, *bhat[2] = {nullptr, nullptr};
+                      double span[2] = {0, 0}; int kmax[2] = {0, 0}; bool built = false; };
+    std::vector<ViewTabs> vtabs;
+    double2* vroots[2] = {nullptr, nullptr};
     bool R_valid = false;             // lanes[last_lane].R holds the last frame (a fused plan: only after the pre-sharpen tap has run)
 
     // device memory
@@ -125,6 +132,7 @@ struct fftup_plan : PlanGeometry {   // the decisions (plan_rules.hpp) + what li
 
 // ---- fftup_plan.hip
 int dev_alloc(fftup_plan* P, void** ptr, size_t bytes);           // hipMalloc owned by the plan
+int view_frames_prepare(fftup_plan* P, int nl);                   // fftup_execute_device_views: the table sets of lanes [0, nl), the fp64 roots, on first use
 inline DeviceFacts device_facts(const hipDeviceProp_t& prop)
 {
     return {prop.sharedMemPerBlock ? prop.sharedMemPerBlock : 65536, prop.multiProcessorCount, prop.gcnArchName};
@@ -140,6 +148,7 @@ inline int check_slot(fftup_plan* P, uint32_t slot)
 
 // ---- fftup_launch.hip: everything that names a kernel (each instantiation once, in the selector of its pass and family)
 // (the facts about the kernels the planner needs: plan_rules.hpp)
+int kernels_allow_view_tables(const fftup_plan* P);                // ... and for k_view_tables, when the plan first runs frames with views of their own
 int kernels_set_attributes(fftup_plan* P);                        // dynamic LDS sizes above 64 KB, for the kernels launch_frame's selectors give THIS plan
 // One frame: its caller names all of it in a FrameRun, nothing about the frame being launched lives in the plan.  Pass: rows ..
 // sharpen are the indices of fftup_profile_kernels / fftup_execute_ring_timed; presharpen_tap = the stand-alone inverse rows of
@@ -149,7 +158,9 @@ enum class Pass { rows, columns, inverse, sharpen, all, presharpen_tap };
 struct DeviceInput { const void* in = nullptr; int kind = 0; long in_row = 0, in_plane = 0; };
 // in_slot: the ring slot the frame reads (`in`: instead of the slot); out: the image its last kernel writes -- a slot's, an extra
 // one of fftup_execute, caller memory, a lane's scratch
-struct FrameRun { int lane = 0; uint32_t in_slot = 0; void* out = nullptr; const DeviceInput* in = nullptr; Pass pass = Pass::all; };
+// view: the frame's own view (fftup_execute_device_views; nullptr: the plan's) -- its tables are built on the lane's stream first
+struct FrameRun { int lane = 0; uint32_t in_slot = 0; void* out = nullptr; const DeviceInput* in = nullptr; Pass pass = Pass::all;
+                  const fftup_view* view = nullptr; };
 int launch_frame(fftup_plan* P, const FrameRun& r);               // launches, then records what the frame left: the only writer of last_lane and R_valid (but see fftup_execute)
 void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st);                  // the host loop of VR:1636-1685 as a kernel
 void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st);      // ... and of VR:1708-1748
