@@ -526,6 +526,64 @@ FFTUP_API int fftup_device_copy(void* dst, const void* src, size_t bytes, int ki
 FFTUP_API int fftup_stream_create(int device, void** stream);
 FFTUP_API int fftup_stream_destroy(void* stream);
 
+/* EXTENSION: shift estimates -- what a view per frame needs to stabilise a clip.  An ALIGNER is a small object beside the plan: for
+ * pairs of frames in device memory, fftup_align_shifts estimates the translation between ref[i] and cur[i] by band-limited
+ * phase-only correlation with a sub-pixel refinement, entirely on the GPU.  dx, dy are in input pixels, cur(x, y) ~ ref(x - dx, y - dy):
+ * a view of cur at origin + (dx, dy) shows what the same view of ref shows at origin.
+ * Detect the feature by these symbols; fftup_version() and FFTUP_ABI_VERSION are unchanged.
+ *
+ * Geometry (arithmetic on the configuration, decided before any device access; fftup_last_error names the rule;
+ * fftup_align_get_info reports it).  The frames are box-averaged over d x d pixels and a centred window of n_x x n_y decimated
+ * pixels is correlated: crop_x = (W - n_x d) / 2, crop_y alike.  decimate = 0: the smallest d of 1, 2, 4, 8 for which the largest
+ * powers of two <= W / d and <= H / d are both <= 1024 (none: 8, the window capped at 1024); window = 0: those powers of two.
+ * FFTUP_E_INVALID_ARG: a window that is not a power of two in [16, 1024] or with window * d above the frame, d not 1, 2, 4 or 8,
+ * a frame below 16 decimated pixels on an axis, band outside (0, 1], upsample outside [4, 64]; FFTUP_E_UNSUPPORTED_PRECISION:
+ * precision 1.  band_kx = floor(band n_x / 2), band_ky alike; K = the number of bins k (signed, -n/2 <= k < n/2 per axis) with
+ * |k_x| <= band_kx and |k_y| <= band_ky.
+ *
+ * The estimate, per pair (fp32 arithmetic, the sums of step 5 in fp64; tests/align_oracle.py restates it in fp64):
+ *   1. luma = 0.2126 R + 0.7152 G + 0.0722 B (RGB8: code / 255; PLANAR: the stored value), box mean over d x d, crop, times the
+ *      separable window w[n] = 1/2 - 1/2 cos(2 pi (n + 1/2) / N): a (ref) and b (cur).
+ *   2. ONE complex transform Z = DFT2(a + i b); A[k] = (Z[k] + conj Z[-k]) / 2, B[k] = (Z[k] - conj Z[-k]) / 2i.
+ *   3. P = B conj(A), R = P / |P|; R = 0 outside the band and where |P| <= 1e-9 |P[0,0]|.
+ *   4. r = Re IDFT2(R); coarse peak p = argmax over the n_x x n_y grid (lowest row-major index on a tie),
+ *      peak_coarse = r_max n_x n_y / K (identical frames: 1).
+ *   5. r(u, v) = (1 / n_x n_y) Re sum_k R[k] exp(2 pi i (k_x u / n_x + k_y v / n_y)) on the (2 kappa + 1)^2 points
+ *      (p_x + i / kappa, p_y + j / kappa), |i|, |j| <= kappa; argmax (same tie rule); per axis the vertex delta of the parabola
+ *      through the maximum and its two fine neighbours (0 on the grid's edge or for a zero denominator);
+ *      peak = the fine maximum times n_x n_y / K.
+ *   6. s = p + (i + delta) / kappa, wrapped to [-n/2, n/2) per axis; dx = d s_x, dy = d s_y.
+ *
+ * Ordering and containment, as fftup_execute_device: everything is enqueued on `stream`, the host is never synchronised, the
+ * descriptor arrays are read before the call returns; the frames are only read; exactly n_pairs * sizeof(fftup_shift) bytes of
+ * shifts_device are written.  ref[i] and cur[i] may alias other pairs' images (a fixed reference, consecutive frames).  The
+ * buffers of max_batch pairs are allocated at creation, fftup_align_shifts allocates nothing; a longer call runs in chunks, in
+ * stream order.  One host thread per aligner at a time.
+ * Validation happens before any launch: FFTUP_E_INVALID_ARG for null pointers, n_pairs == 0 and every descriptor rule of
+ * fftup_execute_device (format, strides, device memory of the aligner's device -- shifts_device too, which must be a multiple of 4). */
+typedef struct fftup_align_config {
+    uint32_t width, height;      /* the frames' size */
+    uint32_t precision;          /* element type of FFTUP_FMT_PLANAR frames: 0 float, 2 IEEE half (1: FFTUP_E_UNSUPPORTED_PRECISION) */
+    int32_t  device;
+    uint32_t window_w, window_h; /* correlation window in decimated pixels: powers of two in [16, 1024]; 0 = automatic */
+    uint32_t decimate;           /* d: box-average d x d input pixels first; 1, 2, 4 or 8; 0 = automatic */
+    float    band;               /* share of each axis' Nyquist range that is correlated, (0, 1]; 0 = 0.5 */
+    uint32_t upsample;           /* kappa: fine-grid points per window pixel, 4..64; 0 = 32 */
+    uint32_t max_batch;          /* pairs whose buffers are held; 0 = 16; longer calls run in chunks */
+} fftup_align_config;
+typedef struct fftup_shift { float dx, dy, peak, peak_coarse; } fftup_shift;
+typedef struct fftup_align fftup_align;
+typedef struct fftup_align_info {
+    uint32_t window_w, window_h, decimate, crop_x, crop_y, upsample, band_kx, band_ky, num_kernels;
+    uint64_t device_bytes;
+    char     kernel_names[8][64];
+} fftup_align_info;
+FFTUP_API int fftup_align_create(fftup_align** out, const fftup_align_config* cfg);
+FFTUP_API void fftup_align_destroy(fftup_align* a);
+FFTUP_API int fftup_align_get_info(const fftup_align* a, fftup_align_info* info);
+FFTUP_API int fftup_align_shifts(fftup_align* a, const fftup_device_image* ref, const fftup_device_image* cur,
+                                 uint32_t n_pairs, fftup_shift* shifts_device, void* stream /* hipStream_t; NULL = the default stream */);
+
 FFTUP_API const char* fftup_strerror(int code);
 FFTUP_API const char* fftup_last_error(void);   /* thread-local detail of the last failure */
 FFTUP_API const char* fftup_version(void);

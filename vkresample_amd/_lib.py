@@ -41,6 +41,7 @@ EXPORTS = [
     "fftup_plan_create_size", "fftup_execute_device", "fftup_device_alloc", "fftup_device_free", "fftup_device_copy",
     "fftup_stream_create", "fftup_stream_destroy", "fftup_plan_create_view", "fftup_plan_set_view",
     "fftup_execute_device_views", "fftup_download_view_tables",
+    "fftup_align_create", "fftup_align_destroy", "fftup_align_get_info", "fftup_align_shifts",
 ]
 ABI_VERSION = 2
 
@@ -68,6 +69,25 @@ class DeviceImageDesc(C.Structure):
 class View(C.Structure):
     """fftup_view: the rectangle of the frame a view plan shows, origin and span per axis in input pixels"""
     _fields_ = [("origin_x", C.c_double), ("origin_y", C.c_double), ("span_x", C.c_double), ("span_y", C.c_double)]
+
+
+class AlignConfig(C.Structure):
+    """fftup_align_config"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("precision", C.c_uint32), ("device", C.c_int32),
+                ("window_w", C.c_uint32), ("window_h", C.c_uint32), ("decimate", C.c_uint32), ("band", C.c_float),
+                ("upsample", C.c_uint32), ("max_batch", C.c_uint32)]
+
+
+class Shift(C.Structure):
+    """fftup_shift: cur(x, y) ~ ref(x - dx, y - dy), in input pixels"""
+    _fields_ = [("dx", C.c_float), ("dy", C.c_float), ("peak", C.c_float), ("peak_coarse", C.c_float)]
+
+
+class AlignInfo(C.Structure):
+    """fftup_align_info"""
+    _fields_ = [("window_w", C.c_uint32), ("window_h", C.c_uint32), ("decimate", C.c_uint32), ("crop_x", C.c_uint32),
+                ("crop_y", C.c_uint32), ("upsample", C.c_uint32), ("band_kx", C.c_uint32), ("band_ky", C.c_uint32),
+                ("num_kernels", C.c_uint32), ("device_bytes", C.c_uint64), ("kernel_names", (C.c_char * 64) * 8)]
 
 
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
@@ -136,5 +156,10 @@ def load():
     lib.fftup_device_copy.argtypes = [vp, vp, sz, C.c_int, vp]
     lib.fftup_stream_create.argtypes = [C.c_int, C.POINTER(vp)]
     lib.fftup_stream_destroy.argtypes = [vp]
+    lib.fftup_align_create.argtypes = [C.POINTER(vp), C.POINTER(AlignConfig)]
+    lib.fftup_align_destroy.argtypes = [vp]
+    lib.fftup_align_destroy.restype = None
+    lib.fftup_align_get_info.argtypes = [vp, C.POINTER(AlignInfo)]
+    lib.fftup_align_shifts.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp, vp]
     _libs[path] = lib
     return lib

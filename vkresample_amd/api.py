@@ -365,6 +365,69 @@ class DeviceBuffer:
             pass
 
 
+class Aligner:
+    """Shift estimates between pairs of frames in device memory (fftup_align_*, include/fftup.h): band-limited phase-only correlation
+    with a sub-pixel refinement, on the GPU.  `window`: (window_w, window_h) in decimated pixels or None (automatic); the zeros of
+    the other arguments are the library's defaults.  `.info`: the geometry in effect and the kernel names."""
+
+    def __init__(self, width, height, precision=0, device=0, window=None, decimate=0, band=0.0, upsample=0, max_batch=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        w = window or (0, 0)
+        cfg = _lib.AlignConfig(width, height, precision, device, w[0], w[1], decimate, band, upsample, max_batch)
+        _check(self._lib.fftup_align_create(C.byref(self._h), C.byref(cfg)), "fftup_align_create")
+        raw = _lib.AlignInfo()
+        _check(self._lib.fftup_align_get_info(self._h, C.byref(raw)), "fftup_align_get_info")
+        self.info = {k: int(getattr(raw, k)) for k in ("window_w", "window_h", "decimate", "crop_x", "crop_y", "upsample", "band_kx",
+                                                        "band_ky", "num_kernels", "device_bytes")}
+        self.info["kernel_names"] = [bytes(n).split(b"\0")[0].decode() for n in raw.kernel_names][:raw.num_kernels]
+        self.width, self.height, self.precision, self.device = width, height, precision, device
+
+    def close(self):
+        if self._h:
+            self._lib.fftup_align_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def shifts_device(self, refs, curs, out_ptr, stream=None):
+        """Pair i = (refs[i], curs[i]), DeviceImages of width x height (one image or a sequence per side; a single ref is repeated for
+        every cur): its fftup_shift goes to out_ptr + 16 i, device memory.  Asynchronous: ordered on `stream`, nothing waits here."""
+        cs = [curs] if isinstance(curs, DeviceImage) else list(curs)
+        rs = [refs] * len(cs) if isinstance(refs, DeviceImage) else list(refs)
+        if len(rs) != len(cs):
+            raise ValueError("shifts_device: %d reference frames, %d current frames" % (len(rs), len(cs)))
+        a = (_lib.DeviceImageDesc * len(rs))(*[r.desc() for r in rs])
+        b = (_lib.DeviceImageDesc * len(cs))(*[c.desc() for c in cs])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_align_shifts(self._h, a, b, len(cs), out_ptr, s), "fftup_align_shifts")
+
+    def shifts(self, refs, curs, stream=None):
+        """-> (n, 4) float32: dx, dy, peak, peak_coarse per pair, cur(x, y) ~ ref(x - dx, y - dy).  Blocking: allocates the result
+        buffer, runs shifts_device and copies back on `stream`."""
+        n = 1 if isinstance(curs, DeviceImage) else len(curs)
+        with DeviceBuffer(max(1, n) * 16, self.device) as buf:
+            self.shifts_device(refs, curs, buf.ptr, stream)
+            return buf.download(stream=stream).view(np.float32).reshape(n, 4).copy()
+
+
+def stabilised_views(view, shifts):
+    """The `views` of Upscaler.execute_device_views that undo the estimated motion: frame i is shown at view's origin + (dx_i, dy_i),
+    so it shows what the reference frame shows at the origin.  view: (origin, span); shifts: rows of Aligner.shifts (or (dx, dy) pairs)."""
+    (ox, oy), span = view
+    return [((float(ox) + float(s[0]), float(oy) + float(s[1])), (float(span[0]), float(span[1]))) for s in shifts]
+
+
 class PinnedArray:
     """uint8 numpy view of page-locked host memory from fftup_host_alloc (needed for truly asynchronous copies
     in Upscaler.submit_rgb8); free with .close() after the frames using it have been waited for."""

@@ -26,6 +26,8 @@
 //   -mirror       with -size and -view: FFTUP_FLAG_MIRROR -- the frame is continued by its reflection instead: no wrap at the borders
 //   -viewto ox,oy,sx,sy -frames K  with -size and -view: one image, K frames whose view moves from -view to -viewto, in ONE
 //                 fftup_execute_device_views call on device buffers; K files, -o NAME.png -> NAME_0001.png ...
+//   -stabilise    batched mode with -size [-view] [-mirror]: fftup_align_shifts estimates every frame's shift against frame 000001,
+//                 fftup_execute_device_views shows each frame at the view moved by its shift
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -68,6 +70,7 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     fftup_view view{};
     uint32_t frames = 0;                     // -viewto ox,oy,sx,sy -frames K: a clip of K views from `view` to `viewTo` (0: none)
     fftup_view viewTo{};
+    bool stabilise = false;                  // -stabilise: batched mode, every frame shown where frame 000001 shows the view
 };
 
 // frame k of the K views of a move from a to b, t = k / (K - 1): per axis the origin linear in t, the span geometric; the ends exact
@@ -129,6 +132,84 @@ static int run_view_clip(const ResampleConfiguration& config, fftup_plan* plan, 
         std::string err;
         if (!pngio::write_rgb8(name.c_str(), host.data() + outBytes * k, (int)uW, (int)uH, (size_t)uW * 3, err))
             printf("Could not write %s: %s\n", name.c_str(), err.c_str());
+    }
+    return FFTUP_OK;
+}
+
+// -stabilise: a folder of frames, frame 000001 the reference.  Every frame goes to device memory once; fftup_align_shifts estimates
+// each frame's shift against the reference (one call, the aligner batches); fftup_execute_device_views renders frame k at the view's
+// origin + its shift, so every output shows what the reference shows; one "frame %06d: shift dx dy peak p" line per frame
+static int run_stabilise(const ResampleConfiguration& config)
+{
+    const int N = config.numFiles;
+    std::vector<uint8_t> frames, one;
+    int width = 0, height = 0;
+    for (int f = 0; f < N; f++) {
+        char name[1024];
+        int w = 0, h = 0, channels = 0;
+        std::string err;
+        snprintf(name, sizeof name, "%s/%06d.png", config.ifolder_prefix, f + 1);
+        if (!pngio::load_rgb8(name, one, w, h, channels, err) || (f && (w != width || h != height))) {
+            printf("Could not load %s: %s\n", name, err.empty() ? "its size differs from frame 000001's" : err.c_str());
+            return FFTUP_E_INCOMPLETE;
+        }
+        if (!f) { width = w; height = h; frames.resize((size_t)N * w * h * 3); }
+        memcpy(frames.data() + (size_t)f * width * height * 3, one.data(), (size_t)width * height * 3);
+    }
+    const uint32_t uW = config.outWidth, uH = config.outHeight;
+    const size_t inBytes = (size_t)width * height * 3, outBytes = (size_t)uW * uH * 3;
+    const fftup_view view = config.hasView ? config.view : fftup_view{0.0, 0.0, (double)width, (double)height};
+    fftup_config cfg{};
+    cfg.width = (uint32_t)width; cfg.height = (uint32_t)height; cfg.channels = 3; cfg.upscale = 1.0f;
+    cfg.precision = config.precision; cfg.sharpen = config.sharpenConst; cfg.device = config.device_id; cfg.flags = config.flags; cfg.ring = 1;
+    fftup_align_config acfg{};
+    acfg.width = (uint32_t)width; acfg.height = (uint32_t)height; acfg.device = config.device_id;
+    fftup_plan* plan = nullptr;
+    fftup_align* aligner = nullptr;
+    int res = fftup_plan_create_view(&plan, &cfg, uW, uH, &view);
+    if (res == FFTUP_OK) res = fftup_align_create(&aligner, &acfg);
+    void* din = res == FFTUP_OK ? fftup_device_alloc(config.device_id, inBytes * N) : nullptr;
+    void* dout = res == FFTUP_OK ? fftup_device_alloc(config.device_id, outBytes * N) : nullptr;
+    void* dshift = res == FFTUP_OK ? fftup_device_alloc(config.device_id, sizeof(fftup_shift) * N) : nullptr;
+    if (res == FFTUP_OK && !(din && dout && dshift)) res = FFTUP_E_OUT_OF_MEMORY;
+    std::vector<fftup_shift> shifts((size_t)N);
+    std::vector<uint8_t> host(res == FFTUP_OK ? outBytes * N : 0);
+    if (res == FFTUP_OK) res = fftup_device_copy(din, frames.data(), inBytes * N, 0, nullptr);
+    if (res == FFTUP_OK) {
+        std::vector<fftup_device_image> ref((size_t)N), in((size_t)N), out((size_t)N);
+        for (int f = 0; f < N; f++) {
+            ref[f] = {din, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            in[f] = {(uint8_t*)din + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            out[f] = {(uint8_t*)dout + outBytes * f, FFTUP_FMT_RGB8, (size_t)uW * 3, 0};
+        }
+        res = fftup_align_shifts(aligner, ref.data(), in.data(), (uint32_t)N, (fftup_shift*)dshift, nullptr);
+        if (res == FFTUP_OK) res = fftup_device_copy(shifts.data(), dshift, sizeof(fftup_shift) * N, 1, nullptr);   // (ordered behind the estimates, blocking)
+        std::vector<fftup_view> views((size_t)N, view);
+        for (int f = 0; f < N && res == FFTUP_OK; f++) {
+            views[f].origin_x += (double)shifts[f].dx;
+            views[f].origin_y += (double)shifts[f].dy;
+            printf("frame %06d: shift %.3f %.3f peak %.3f\n", f + 1, shifts[f].dx, shifts[f].dy, shifts[f].peak);
+        }
+        if (res == FFTUP_OK) res = fftup_execute_device_views(plan, in.data(), out.data(), views.data(), (uint32_t)N, nullptr);
+        if (res == FFTUP_OK) res = fftup_device_copy(host.data(), dout, outBytes * N, 1, nullptr);
+    }
+    fftup_device_free(din);
+    fftup_device_free(dout);
+    fftup_device_free(dshift);
+    fftup_align_destroy(aligner);
+    fftup_plan_destroy(plan);
+    if (res != FFTUP_OK) {
+        printf("Stabilisation failed: %s (%s)\n", fftup_strerror(res), fftup_last_error());
+        return res;
+    }
+    for (int f = 0; f < N; f++) {
+        char name[1024];
+        std::string err;
+        snprintf(name, sizeof name, "%s/%06d.png", config.ofolder_prefix, f + 1);
+        if (!pngio::write_rgb8(name, host.data() + outBytes * f, (int)uW, (int)uH, (size_t)uW * 3, err)) {
+            printf("Could not write %s: %s\n", name, err.c_str());
+            return FFTUP_E_INCOMPLETE;
+        }
     }
     return FFTUP_OK;
 }
@@ -450,6 +531,7 @@ int main(int argc, char* argv[])
         printf("	-view OX,OY,SX,SY: with -size: show the rectangle of the image that starts at position (OX, OY) and spans SX x SY input pixels, e.g. -size 1920x1080 -view 480,270,960,540 on 1920x1080: a 2x zoom about the centre; any real numbers (sub-pixel pan, any ratio; the image is periodic; a step SX/W outside [1/64, 8] is refused; not with -centres)\n");
         printf("	-mirror: with -size and -view: continue the image by its reflection instead of periodically: no wrap-around at the borders, e.g. -size 1920x1080 -view -0.144,-0.144,1366,768 -mirror -anysize on 1366x768 (-p 0 and -p 2, not with -dct)\n");
         printf("	-viewto OX,OY,SX,SY -frames K: with -size and -view, single image mode: a clip of K frames (2 to 9999) whose view moves from -view to -viewto (position linear, span geometric); -o NAME.png gives NAME_0001.png ...; the views are printed, one 'view k: ox oy sx sy' line each\n");
+        printf("	-stabilise: batched mode with -size [-view] [-mirror]: frame 000001 is the reference; every frame's shift against it is estimated on the GPU (phase correlation) and the frame is shown at the view moved by that shift; one 'frame N: shift dx dy peak p' line each; one thread, one device\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -542,6 +624,18 @@ int main(int argc, char* argv[])
     }
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");
+    config.stabilise = findFlag(B, E, "-stabilise");
+    if (config.stabilise) {
+        // what the mode cannot serve: one line, exit code 1
+        if (findFlag(B, E, "-i") || !findFlag(B, E, "-ifolder")) { printf("-stabilise works on a folder of frames (-ifolder, -ofolder, -numfiles): it cannot be combined with -i\n"); return 1; }
+        if (!config.outWidth) { printf("-stabilise needs an output size given with -size (-u cannot be used)\n"); return 1; }
+        if (config.frames) { printf("-stabilise follows the measured motion: it cannot be combined with -viewto\n"); return 1; }
+        if (config.gpuPng) { printf("-stabilise writes its files on the host: it cannot be combined with -gpupng\n"); return 1; }
+        if (config.align == FFTUP_ALIGN_CENTRE) { printf("-stabilise places the output pixels itself: it cannot be combined with -centres\n"); return 1; }
+        int nt = 1;
+        if (findFlag(B, E, "-numthreads")) { char* v = getFlagValue(B, E, "-numthreads"); if (v) sscanf(v, "%d", &nt); }
+        if (nt > 1) { printf("-stabilise runs on one thread and one device: it cannot be combined with -numthreads above 1\n"); return 1; }
+    }
 
     if (!findFlag(B, E, "-ifolder")) {
         config.fileUpload = 0;
@@ -568,6 +662,7 @@ int main(int argc, char* argv[])
         if (config.numThreads < 1) config.numThreads = 1;
         if (config.numFiles < 1) { printf("No numFiles is selected with -numfiles flag\n"); return 1; }
     }
+    if (config.stabilise) return run_stabilise(config) == FFTUP_OK ? 0 : 1;
     std::atomic<int> queue{0};
     if (config.fileUpload && findFlag(B, E, "-workqueue")) config.workQueue = &queue;
     auto timeSubmit = std::chrono::system_clock::now();

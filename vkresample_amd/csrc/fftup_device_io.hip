@@ -10,16 +10,8 @@
 
 #include "plan.hpp"
 
-namespace {
-
-// one side of one frame, decided from the descriptor alone (nothing here touches the memory)
-struct Route {
-    bool in_place = false;   // the frame kernel reads / writes `data` itself
-    int gran = 1;            // otherwise: the copy kernel's granularity
-};
-
-// every rule of include/fftup.h for one descriptor; `w` x `h`: the image it names
-int check_image(const fftup_plan* P, const fftup_device_image& im, const char* side, uint32_t i, uint32_t w, uint32_t h, bool is_out)
+// every rule of include/fftup.h for one descriptor; `w` x `h`: the image it names (plan.hpp: fftup_align_shifts checks with it too)
+int check_device_image(size_t esz, bool u8out, int device, const fftup_device_image& im, const char* side, uint32_t i, uint32_t w, uint32_t h, bool is_out)
 {
     const std::string at = std::string(side) + "[" + std::to_string(i) + "]";
     if (!im.data) return fail(FFTUP_E_INVALID_ARG, at + ".data is null");
@@ -28,16 +20,16 @@ int check_image(const fftup_plan* P, const fftup_device_image& im, const char* s
         if (im.row_stride_bytes < (size_t)3 * w)
             return fail(FFTUP_E_INVALID_ARG, at + ".row_stride_bytes " + std::to_string(im.row_stride_bytes) + " is below one row of " + std::to_string((size_t)3 * w) + " bytes");
     } else {
-        if (is_out && P->u8out)
+        if (is_out && u8out)
             return fail(FFTUP_E_INVALID_ARG, at + ": the plan stores 8-bit RGB only (FFTUP_FLAG_FUSE_U8_STORE), it has no planes: use FFTUP_FMT_RGB8");
-        if (im.row_stride_bytes < (size_t)w * P->esz)
-            return fail(FFTUP_E_INVALID_ARG, at + ".row_stride_bytes " + std::to_string(im.row_stride_bytes) + " is below one row of " + std::to_string((size_t)w * P->esz) + " bytes");
-        if (im.row_stride_bytes % P->esz)
-            return fail(FFTUP_E_INVALID_ARG, at + ".row_stride_bytes " + std::to_string(im.row_stride_bytes) + " is not a multiple of the element size " + std::to_string(P->esz));
+        if (im.row_stride_bytes < (size_t)w * esz)
+            return fail(FFTUP_E_INVALID_ARG, at + ".row_stride_bytes " + std::to_string(im.row_stride_bytes) + " is below one row of " + std::to_string((size_t)w * esz) + " bytes");
+        if (im.row_stride_bytes % esz)
+            return fail(FFTUP_E_INVALID_ARG, at + ".row_stride_bytes " + std::to_string(im.row_stride_bytes) + " is not a multiple of the element size " + std::to_string(esz));
         if (im.plane_stride_bytes < (size_t)h * im.row_stride_bytes)
             return fail(FFTUP_E_INVALID_ARG, at + ".plane_stride_bytes " + std::to_string(im.plane_stride_bytes) + " is below height * row_stride_bytes");
-        if (im.plane_stride_bytes % P->esz)
-            return fail(FFTUP_E_INVALID_ARG, at + ".plane_stride_bytes " + std::to_string(im.plane_stride_bytes) + " is not a multiple of the element size " + std::to_string(P->esz));
+        if (im.plane_stride_bytes % esz)
+            return fail(FFTUP_E_INVALID_ARG, at + ".plane_stride_bytes " + std::to_string(im.plane_stride_bytes) + " is not a multiple of the element size " + std::to_string(esz));
     }
     hipPointerAttribute_t a{};
     const hipError_t e = hipPointerGetAttributes(&a, im.data);
@@ -46,8 +38,21 @@ int check_image(const fftup_plan* P, const fftup_device_image& im, const char* s
         return fail(FFTUP_E_INVALID_ARG, at + ".data is not device memory (hipPointerGetAttributes: " + hipGetErrorString(e) + ")");
     }
     if (a.type != hipMemoryTypeDevice) return fail(FFTUP_E_INVALID_ARG, at + ".data is not device memory");
-    if (a.device != P->device) return fail(FFTUP_E_INVALID_ARG, at + ".data is device memory of device " + std::to_string(a.device) + ", the plan runs on device " + std::to_string(P->device));
+    if (a.device != device) return fail(FFTUP_E_INVALID_ARG, at + ".data is device memory of device " + std::to_string(a.device) + ", the plan runs on device " + std::to_string(device));
     return FFTUP_OK;
+}
+
+namespace {
+
+// one side of one frame, decided from the descriptor alone (nothing here touches the memory)
+struct Route {
+    bool in_place = false;   // the frame kernel reads / writes `data` itself
+    int gran = 1;            // otherwise: the copy kernel's granularity
+};
+
+int check_image(const fftup_plan* P, const fftup_device_image& im, const char* side, uint32_t i, uint32_t w, uint32_t h, bool is_out)
+{
+    return check_device_image(P->esz, P->u8out, P->device, im, side, i, w, h, is_out);
 }
 
 // Input planes run in place when `data` is a multiple of the element size: every first kernel of a frame (load_px, load_px_t: the

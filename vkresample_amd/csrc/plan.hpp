@@ -9,6 +9,7 @@
 //   fftup_queue.hip    host-streamed frames: fftup_submit_rgb8 / fftup_wait / fftup_drain
 //   fftup_png.hip      the device-side PNG encoder's host side
 //   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views and the device / stream helpers
+//   fftup_align.hip    shift estimates: the aligner object (fftup_align_*), beside the plan, and the launches of kernels_align.hpp
 //   jit.cpp            the plan-time compiler
 #pragma once
 #include <hip/hip_runtime.h>
@@ -180,6 +181,11 @@ void launch_copy_rows(const void* src, size_t src_row, size_t src_plane, void* d
 int lanes_fork(fftup_plan* P, hipEvent_t ev, hipStream_t from, int first, int nl);
 int lanes_join(fftup_plan* P, int first, int nl, std::initializer_list<hipStream_t> into, int rc);
 int execute_ring_impl(fftup_plan* P, uint32_t n_frames, uint32_t first_slot, double* ms_total, double* kernel_ms, uint32_t stride);
+
+// ---- fftup_device_io.hip
+// every rule of include/fftup.h for one fftup_device_image naming a `w` x `h` image of `device` (esz: bytes of a PLANAR element; u8out:
+// PLANAR output is refused), the memory itself untouched.  Shared by fftup_execute_device and fftup_align_shifts (fftup_align.hip)
+int check_device_image(size_t esz, bool u8out, int device, const fftup_device_image& im, const char* side, uint32_t i, uint32_t w, uint32_t h, bool is_out);
 
 // ---- fftup_queue.hip
 int submit_frame(fftup_plan* P, const uint8_t* rgb_in, size_t in_stride, uint8_t* rgb_out, size_t out_stride, bool png, uint64_t* ticket);

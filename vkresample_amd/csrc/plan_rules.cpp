@@ -627,3 +627,54 @@ int plan_geometry_finish(PlanGeometry& G, const DeviceFacts& dev, const fftup_ji
     G.coef = const_via_percent_f((double)G.cfg.sharpen, G.half);                     // VkResample.cpp:1616
     return FFTUP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ align_geometry
+// fftup_align_create: the rules and decisions of an aligner (include/fftup.h), arithmetic on the configuration alone
+static uint32_t pow2_floor(uint32_t v)
+{
+    uint32_t p = 1;
+    while (p <= v / 2) p *= 2;
+    return v ? p : 0;
+}
+
+int align_geometry(const fftup_align_config& c, AlignGeometry& G)
+{
+    const char* who = "fftup_align_create: ";
+    if (c.width == 0 || c.height == 0) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "width and height must be > 0");
+    if (c.width > (1u << 16) || c.height > (1u << 16)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "width/height above 65536");
+    if (c.precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes): there are no -p 1 frames");
+    if (c.precision > 2) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes)");
+    if (c.decimate != 0 && c.decimate != 1 && c.decimate != 2 && c.decimate != 4 && c.decimate != 8)
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "decimate " + std::to_string(c.decimate) + " must be 1, 2, 4 or 8 (0: automatic)");
+    const uint32_t win[2] = {c.window_w, c.window_h};
+    for (int a = 0; a < 2; a++)
+        if (win[a] && (win[a] < 16 || win[a] > 1024 || (win[a] & (win[a] - 1))))
+            return fail(FFTUP_E_INVALID_ARG, std::string(who) + (a ? "window_h " : "window_w ") + std::to_string(win[a]) + " must be a power of two in [16, 1024] (0: automatic)");
+    if (!(c.band == 0.0f || (c.band > 0.0f && c.band <= 1.0f))) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "band must lie in (0, 1] (0: 0.5)");
+    if (c.upsample && (c.upsample < 4 || c.upsample > 64)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "upsample " + std::to_string(c.upsample) + " must lie in [4, 64] (0: 32)");
+    if (c.max_batch > 65535) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "max_batch must be <= 65535");
+    G.W = c.width; G.H = c.height; G.precision = c.precision;
+    G.band = c.band == 0.0f ? 0.5f : c.band;
+    G.kappa = c.upsample ? c.upsample : 32;
+    G.max_batch = c.max_batch ? c.max_batch : 16;
+    // automatic d: the smallest whose automatic windows are both at most 1024; none: 8, the windows capped
+    G.d = c.decimate;
+    if (!G.d) {
+        G.d = 8;
+        for (uint32_t d : {1u, 2u, 4u, 8u})
+            if (pow2_floor(c.width / d) <= 1024 && pow2_floor(c.height / d) <= 1024) { G.d = d; break; }
+    }
+    if (c.width / G.d < 16 || c.height / G.d < 16)
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "a frame of " + std::to_string(c.width) + "x" + std::to_string(c.height) + " has fewer than 16 decimated pixels on an axis (d = " + std::to_string(G.d) + ")");
+    G.nx = c.window_w ? c.window_w : std::min(1024u, pow2_floor(c.width / G.d));
+    G.ny = c.window_h ? c.window_h : std::min(1024u, pow2_floor(c.height / G.d));
+    if ((uint64_t)G.nx * G.d > c.width) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "window_w * d = " + std::to_string((uint64_t)G.nx * G.d) + " exceeds the frame's width " + std::to_string(c.width));
+    if ((uint64_t)G.ny * G.d > c.height) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "window_h * d = " + std::to_string((uint64_t)G.ny * G.d) + " exceeds the frame's height " + std::to_string(c.height));
+    G.crop_x = (c.width - G.nx * G.d) / 2;
+    G.crop_y = (c.height - G.ny * G.d) / 2;
+    G.band_kx = (uint32_t)std::floor((double)G.band * (double)G.nx / 2.0);
+    G.band_ky = (uint32_t)std::floor((double)G.band * (double)G.ny / 2.0);
+    G.Kx = G.band_kx < G.nx / 2 ? 2 * G.band_kx + 1 : G.nx;
+    G.Ky = G.band_ky < G.ny / 2 ? 2 * G.band_ky + 1 : G.ny;
+    return FFTUP_OK;
+}

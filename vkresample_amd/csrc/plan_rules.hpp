@@ -124,4 +124,13 @@ void column_guard(float upscale, uint32_t uH, int* zly, int* zry);   // the zero
 int jit_factor(float upscale, uint32_t W, uint32_t H, uint32_t uW, uint32_t uH, int zly, int zry, int* DD);
 int check_view(const char* who, const fftup_view* v, uint32_t uW, uint32_t uH);
 float view_factor(const fftup_view& v, uint32_t uW, uint32_t uH);
+
+// ---- fftup_align_create: every rule and decision of an aligner (include/fftup.h, "shift estimates"), before any device access.
+// Kx, Ky: the bins in band per axis -- signed k in [-n/2, n/2) with |k| <= band_k, index i = k + band_k; K = Kx Ky
+struct AlignGeometry {
+    uint32_t W = 0, H = 0, precision = 0, nx = 0, ny = 0, d = 1, crop_x = 0, crop_y = 0, kappa = 32, band_kx = 0, band_ky = 0;
+    uint32_t Kx = 0, Ky = 0, max_batch = 16;
+    float band = 0.5f;
+};
+int align_geometry(const fftup_align_config& c, AlignGeometry& G);
 float const_via_percent_f(double v, bool half);
