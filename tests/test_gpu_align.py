@@ -18,13 +18,10 @@ import numpy as np
 import pytest
 
 import align_oracle as AO
-from test_gpu_dct import _png_read, _png_write
-from test_gpu_device_io import FILL, GUARD, PLANAR, RGB8, _Image
-from test_gpu_oddsize import _m, _rel_l2
+from devimage import FILL, GUARD, PLANAR, RGB8, Image
+from paritylib import CLI, measured, png_read, png_write, rel_l2
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 
 KAPPA = 32
 PEAK_BAR = 4 * 2.4e-7
@@ -62,7 +59,7 @@ def _oracle(case, fmt):
 def _images(case, fmt, frames, padded=False, base=GUARD):
     W, H = case[0], case[1]
     dfmt, _, esz, conv = FORMATS[fmt]
-    return [_Image(dfmt, W, H, esz, padded, base, conv(f)) for f in frames]
+    return [Image(dfmt, W, H, esz, padded, base, conv(f)) for f in frames]
 
 
 def _aligner(case, fmt, **kw):
@@ -99,8 +96,8 @@ def test_parity_with_the_oracle(case, fmt):
         _close(ims)
     assert got.shape == (7, 4) and got.dtype == np.float32
     for k, (g, o) in enumerate(zip(got, oracle)):
-        _m("align %s %s pair %d" % (CASE_IDS[GPU_CASES.index(case)], fmt, k), ddx=abs(g[0] - o["dx"]), ddy=abs(g[1] - o["dy"]),
-           dpeak=abs(g[2] - o["peak"]), dcoarse=abs(g[3] - o["peak_coarse"]), oracle_gap=o["gap"], true_dx=true[k][0], got_dx=g[0])
+        measured("align %s %s pair %d" % (CASE_IDS[GPU_CASES.index(case)], fmt, k), ddx=abs(g[0] - o["dx"]), ddy=abs(g[1] - o["dy"]),
+                 dpeak=abs(g[2] - o["peak"]), dcoarse=abs(g[3] - o["peak_coarse"]), oracle_gap=o["gap"], true_dx=true[k][0], got_dx=g[0])
     for k, o in enumerate(oracle):
         assert o["gap"] > 1e-3, "pair %d: the oracle's coarse argmax is a coin toss (gap %.3g)" % (k, o["gap"])
     for k, (g, o) in enumerate(zip(got, oracle)):
@@ -127,8 +124,8 @@ def test_half_pixel_shifts_on_the_wide_window(fmt):
         _close(ims)
     for k, (g, o) in enumerate(zip(got, oracle)):
         dcoarse = min(abs(g[3] - v) for v in o["near"])
-        _m("align wide half-pixel %s pair %d" % (fmt, k), ddx=abs(g[0] - o["dx"]), ddy=abs(g[1] - o["dy"]), dpeak=abs(g[2] - o["peak"]),
-           dcoarse=dcoarse, oracle_gap=o["gap"], true_dx=true[k][0], got_dx=g[0])
+        measured("align wide half-pixel %s pair %d" % (fmt, k), ddx=abs(g[0] - o["dx"]), ddy=abs(g[1] - o["dy"]), dpeak=abs(g[2] - o["peak"]),
+                 dcoarse=dcoarse, oracle_gap=o["gap"], true_dx=true[k][0], got_dx=g[0])
         assert dcoarse <= PEAK_BAR, (k, g, o)
         assert abs(g[0] - o["dx"]) <= 1 / KAPPA and abs(g[1] - o["dy"]) <= 1 / KAPPA, (k, g, o)
         assert abs(g[2] - o["peak"]) <= PEAK_BAR, (k, g, o)
@@ -147,7 +144,7 @@ def test_identical_frames(fmt):
     finally:
         _close(ims)
     for g in got:
-        _m("align identical %s" % fmt, dx=g[0], dy=g[1], dpeak=abs(g[2] - 1.0), dcoarse=abs(g[3] - 1.0))
+        measured("align identical %s" % fmt, dx=g[0], dy=g[1], dpeak=abs(g[2] - 1.0), dcoarse=abs(g[3] - 1.0))
     for g in got:
         assert g[0] == 0.0 and g[1] == 0.0, got
         assert abs(g[2] - 1.0) <= PEAK_BAR and abs(g[3] - 1.0) <= PEAK_BAR, got
@@ -270,7 +267,7 @@ STAB_VIEW = ((4.0, 2.0), (40.0, 36.0))
 
 
 def _render(up, images, views):
-    outs = [_Image(PLANAR, SUW, SUH, 4) for _ in images]
+    outs = [Image(PLANAR, SUW, SUH, 4) for _ in images]
     try:
         up.execute_device_views([im.image for im in images], [o.image for o in outs], views)
         return [o.read()[0].view(np.float32).astype(np.float64) for o in outs]
@@ -287,7 +284,7 @@ def test_stabilised_clip_end_to_end():
     frames = AO.clip(SW, SH, 1, [(0.0, 0.0)] + STAB_SHIFTS, seed=5)
     g = AO.geometry(SW, SH)
     oracle = [AO.estimate(frames[0], f, g) for f in frames[1:]]
-    ims = [_Image(RGB8, SW, SH, 1, frame=f) for f in frames]
+    ims = [Image(RGB8, SW, SH, 1, frame=f) for f in frames]
     try:
         with v.Aligner(SW, SH) as al:
             assert (al.info["window_w"], al.info["window_h"], al.info["decimate"]) == (g["nx"], g["ny"], g["d"]) == (32, 32, 1)
@@ -302,8 +299,8 @@ def test_stabilised_clip_end_to_end():
         _close(ims)
     figures = []
     for k in range(len(STAB_SHIFTS)):
-        gt, ot, ut = _rel_l2(G[k], T[k]), _rel_l2(Oo[k], T[k]), _rel_l2(U[k], T[k])
-        _m("stabilise frame %d" % k, rel_G_T=gt, rel_O_T=ot, rel_unstabilised_T=ut, dx=est[k][0], dy=est[k][1], oracle_dx=oracle[k]["dx"], oracle_dy=oracle[k]["dy"])
+        gt, ot, ut = rel_l2(G[k], T[k]), rel_l2(Oo[k], T[k]), rel_l2(U[k], T[k])
+        measured("stabilise frame %d" % k, rel_G_T=gt, rel_O_T=ot, rel_unstabilised_T=ut, dx=est[k][0], dy=est[k][1], oracle_dx=oracle[k]["dx"], oracle_dy=oracle[k]["dy"])
         figures.append((gt, ot, ut))
     for gt, ot, ut in figures:
         assert gt <= 2 * ot + 1e-6, figures
@@ -319,8 +316,8 @@ def test_cli_stabilise(tmp_path):
     src.mkdir()
     dst.mkdir()
     for k, f in enumerate(frames):
-        _png_write(str(src / ("%06d.png" % (k + 1))), f)
-    ims = [_Image(RGB8, SW, SH, 1, frame=f) for f in frames]
+        png_write(str(src / ("%06d.png" % (k + 1))), f)
+    ims = [Image(RGB8, SW, SH, 1, frame=f) for f in frames]
     try:
         with v.Aligner(SW, SH) as al:
             est = al.shifts(ims[0].image, [im.image for im in ims])
@@ -336,7 +333,7 @@ def test_cli_stabilise(tmp_path):
         assert abs(float(l[1]) - e[0]) <= 1 / KAPPA + 0.0005 and abs(float(l[2]) - e[1]) <= 1 / KAPPA + 0.0005, (l, e)
     written = sorted(os.listdir(dst))
     assert written == ["%06d.png" % (k + 1) for k in range(4)]
-    assert _png_read(str(dst / written[0])).shape == (SUH, SUW, 3)
+    assert png_read(str(dst / written[0])).shape == (SUH, SUW, 3)
     for extra, text in ((["-numthreads", "2"], "-numthreads above 1"), (["-gpupng"], "-gpupng")):
         r = subprocess.run(args + extra, capture_output=True, text=True, timeout=300)
         assert r.returncode == 1 and text in r.stdout and len(r.stdout.strip().splitlines()) == 1, r.stdout

@@ -1,14 +1,8 @@
 """GPU: FFTUP_FLAG_ANY_SIZE (csrc/kernels_bluestein.hpp; Bluestein forward rows: k_row_r2c_odd of csrc/kernels_odd.hpp) -- sizes with
 a prime factor above 7 -- against the fp64 statement of the reference's filter at that size:
 oracle/ref_layout_emulation.closed_form (quirks B1-B3) followed by oraclelib.sharpen (B4, B5); for FFTUP_FLAG_DOWNSCALE plans
-tests/downscale_oracle.py.
-
-Bars: the project's, as stated at the top of tests/test_gpu_downscale.py.  fp32: the pre-sharpen image y = upsq R within relative L2
-2e-6 and max 1e-5 of full scale; the sharpened output against oraclelib.sharpen applied to the oracle's R within relative L2 5e-6
-and max 2e-5.  fp16 (-p 2): R within one binary16 ulp of the oracle's own binary16 value and different from it in <= 1 % of the
-pixels; output relative L2 <= 3.5e-4, different in <= 2 %, max 8e-3.  The last output row is compared too: its reads
-past the end of a plane, undefined in the reference (quirk B5), are defined here as "same column, last written row"
-(oracle/fftup_oracle.c), and the HIP path is held to that definition.
+tests/downscale_oracle.py.  The bars are those of tests/paritylib.py; the amplitude-preserving image is sc * R, sc = upsq for an
+upscale and (uW uH) / (W H) for a downscale.
 
 Every parity case runs with planar and fused-uint8 input for -p 0 and -p 2, except the two large ones: 1366x768 -u 2 runs -p 0 and
 the downscale 2732x1536 -> 1366x768 runs -p 2 in the default run; FFTUP_BIG_TESTS=1 adds the other precision of each."""
@@ -20,49 +14,19 @@ import pytest
 
 import downscale_oracle as S
 import oraclelib as O
+import paritylib as P
 from oracle import ref_layout_emulation as E
-from test_gpu_dct import _png_pixels, _png_read, _png_write
+from paritylib import CLI
 from test_host_anysize import VALID
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 BIG = os.environ.get("FFTUP_BIG_TESTS", "0") != "0"
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-30))
-
-
-def _m(tag, **vals):
-    print("MEASURED %s: %s" % (tag, "  ".join("%s %.3g" % kv for kv in vals.items())))
-
-
-def _frame(W, H, seed=0, dist="N"):
-    from vkresample_amd import synth
-    return synth.frame(seed, W, H, dist)
-
-
-def _inputs(W, H, precision, uint8, seed):
-    """(rgb, planes, x) as tests/test_gpu_downscale.py: what is uploaded and the values the plan computes on"""
-    rgb = _frame(W, H, seed=seed)
-    if uint8:
-        return rgb, None, O.load_lut(precision)[np.transpose(rgb, (2, 0, 1))]
-    x = np.transpose(rgb, (2, 0, 1)) / 255.0 + np.random.RandomState(seed).rand(3, H, W) / 512.0
-    planes = x.astype(np.float16 if precision == 2 else np.float32)
-    return None, planes, planes.astype(np.float64)
 
 
 def _run(W, H, u, precision, flags, rgb=None, planes=None):
     import vkresample_amd as v
-    with v.Upscaler(W, H, u, precision, 0.2, 0, flags | v.FLAG_ANY_SIZE) as up:
-        if rgb is not None:
-            up.upload_rgb8(rgb)
-        else:
-            up.upload_planar(planes)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
+    with v.Upscaler(W, H, u, precision, P.SHARPEN, 0, flags | v.FLAG_ANY_SIZE) as up:
+        pre, out = P.run_uploaded(up, rgb, planes)
         names, desc = up.kernel_names, up.description
         assert not up.tuned and not up.u8_store
     return pre, out, names, desc
@@ -71,7 +35,7 @@ def _run(W, H, u, precision, flags, rgb=None, planes=None):
 def _check(W, H, u, precision, down, uint8, seed, tag, pooled=None):
     """sc * R is the amplitude-preserving image y: sc = upsq for an upscale, (uW uH) / (W H) for a downscale"""
     import vkresample_amd as v
-    rgb, planes, x = _inputs(W, H, precision, uint8, seed)
+    rgb, planes, x = P.inputs(W, H, precision, uint8, seed)
     flags = (v.FLAG_DOWNSCALE if down else 0) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0)
     pre, out, names, desc = _run(W, H, u, precision, flags, rgb, planes)
     assert any(n.endswith("_bz") for n in names) and "bluestein L=" in desc, (names, desc)
@@ -84,30 +48,7 @@ def _check(W, H, u, precision, down, uint8, seed, tag, pooled=None):
         R = E.closed_form(x, u)
         sc = float(np.float32(u)) ** 2
     assert pre.shape == R.shape == (3, uH, uW)
-    y = sc * R
-    if precision == 0:
-        sh = O.sharpen(R, u, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(sc * pre, y), pre_max=np.abs(sc * pre - y).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max())
-        assert _rel_l2(sc * pre, y) <= 2e-6
-        assert np.abs(sc * pre - y).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           out_diff_frac=(out != sh).mean())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        if pooled is None:
-            assert (pre != opre).mean() <= 0.01
-            assert (out != sh).mean() <= 0.02
-        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
-            pooled.append((int((pre != opre).sum()), pre.size, int((out != sh).sum()), out.size))
+    P.assert_parity(tag, precision, pre, out, sc * R, sc, u, pooled=pooled)
     return pre, x
 
 
@@ -124,8 +65,7 @@ def test_anysize_parity(W, H, u, precision, uint8):
     pre, x = _check(W, H, u, precision, False, uint8, W + H + precision, "anysize p%d %dx%d u%.4g u8%d" % (precision, W, H, u, uint8))
     if u == 1.0 and precision == 0:
         # -u 1 reproduces the input (the oracle does, to 7e-16): nothing is padded, no Nyquist quirk applies
-        _m("anysize identity %dx%d" % (W, H), max_err=np.abs(pre - x).max(), l2=_rel_l2(pre, x))
-        assert _rel_l2(pre, x) <= 2e-6 and np.abs(pre - x).max() <= 1e-5
+        P.assert_identity("anysize identity %dx%d" % (W, H), pre, x)
 
 
 @pytest.mark.parametrize("precision", [0, 2] if BIG else [0])
@@ -156,15 +96,15 @@ def test_single_cosine_comes_back_resampled(k):
     want = np.broadcast_to(0.5 + a * np.cos(2 * np.pi * k * np.arange(2 * W) / (2 * W)), (3, 2 * H, 2 * W))
     # (the fp32 input's own rounding: compare with the exact resampling of the rounded input as well)
     ref = 4.0 * E.closed_form(x.astype(np.float64), 2.0)
-    _m("anysize cosine k=%d" % k, max_err=np.abs(4.0 * pre - want).max(), l2=_rel_l2(4.0 * pre, want), oracle_max=np.abs(ref - want).max())
-    assert _rel_l2(4.0 * pre, want) <= 2e-6
-    assert np.abs(4.0 * pre - want).max() <= 1e-5
+    P.measured("anysize cosine k=%d" % k, max_err=np.abs(4.0 * pre - want).max(), l2=P.rel_l2(4.0 * pre, want), oracle_max=np.abs(ref - want).max())
+    assert P.rel_l2(4.0 * pre, want) <= P.FP32_PRE_L2
+    assert np.abs(4.0 * pre - want).max() <= P.FP32_PRE_MAX
 
 
 @pytest.mark.parametrize("W,H,u,down", [(2048, 1024, 2.0, False), (640, 480, 1.5, False), (4096, 2048, 0.5, True)])
 def test_flag_is_a_no_op_on_smooth_plans(W, H, u, down):
     import vkresample_amd as v
-    rgb = _frame(W, H, seed=5)
+    rgb = P.frame(W, H, seed=5)
     got = []
     for flags in (0, v.FLAG_ANY_SIZE):
         with v.Upscaler(W, H, u, 0, 0.2, 0, flags | (v.FLAG_DOWNSCALE if down else 0)) as up:
@@ -183,7 +123,7 @@ def test_every_execution_path_gives_the_same_bytes(precision):
     import vkresample_amd as v
     W, H, u = 1366, 768, 2.0
     flags = v.FLAG_ANY_SIZE
-    frames = [np.ascontiguousarray(_frame(W, H, seed=60 + k)) for k in range(3)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=60 + k)) for k in range(3)]
     want, planes, sums = [], [], []
     with v.Upscaler(W, H, u, precision, 0.2, 0, flags) as up:
         for f in frames:
@@ -218,7 +158,7 @@ def test_every_execution_path_gives_the_same_bytes(precision):
         buf = np.empty(up.png_bound(), np.uint8)
         for k in (2, 0):
             n = up.wait_png(up.submit_png(frames[k]), buf)
-            assert np.array_equal(_png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
+            assert np.array_equal(P.png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
         # the input tap: what the fused-load row kernel computes on is what the unpack kernel stores
         up.upload_rgb8(frames[1], 0)
         assert np.array_equal(up.download_input_planar(0).astype(np.float64), O.load_lut(precision)[np.transpose(frames[1], (2, 0, 1))])
@@ -228,25 +168,25 @@ def test_anysize_cli(tmp_path):
     """-anysize -u 2 on a 1366x768 PNG gives the API's pixels, single-image and batched; without -anysize the CLI refuses with the
     code's own message and names the option"""
     import vkresample_amd as v
-    rgb = _frame(1366, 768, seed=78)
+    rgb = P.frame(1366, 768, seed=78)
     with v.Upscaler(1366, 768, 2.0, 0, 0.2, 0, v.FLAG_ANY_SIZE) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
         want = up.download_rgb8()
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
     r = subprocess.run([CLI, "-anysize", "-i", "in.png", "-o", "out.png", "-u", "2", "-n", "1"], capture_output=True, text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "out.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "out.png"), want)
     r = subprocess.run([CLI, "-i", "in.png", "-o", "bad.png", "-u", "2", "-n", "1"], capture_output=True, text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 2 and not (tmp_path / "bad.png").exists()
     assert "unsupported size" in r.stdout + r.stderr and "-anysize" in r.stdout + r.stderr
     (tmp_path / "inp").mkdir()
     (tmp_path / "outp").mkdir()
-    _png_write(tmp_path / "inp" / "000001.png", rgb)
+    P.png_write(tmp_path / "inp" / "000001.png", rgb)
     r = subprocess.run([CLI, "-ifolder", "inp", "-ofolder", "outp", "-numfiles", "1", "-u", "2", "-anysize"], capture_output=True, text=True,
                        cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "outp" / "000001.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "outp" / "000001.png"), want)
 
 
 def test_anysize_plan_info_and_errors():

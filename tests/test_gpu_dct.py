@@ -1,61 +1,25 @@
-"""GPU: the DCT upscale mode (FFTUP_FLAG_DCT, csrc/kernels_dct.hpp) against the fp64 matrix oracle of tests/dct_oracle.py.
-
-Bars: those of the FFT path (tests/test_gpu_parity.py).  fp32: the pre-sharpen image y = upsq R within relative L2 2e-6 and max
-1e-5 of full scale; the sharpened output against oraclelib.sharpen applied to the oracle's R within relative L2 5e-6 and max
-2e-5 (natural-like frames).  fp16 (-p 2): R within one binary16 ulp of the oracle's own binary16 value and different from it in
-<= 1 % of the pixels; output relative L2 <= 3.5e-4, different in <= 2 %, max 8e-3.  The last output row is compared too: its reads
-past the end of a plane, undefined in the reference (quirk B5), are defined here as "same column, last written row"
-(oracle/fftup_oracle.c), and the HIP path is held to that definition.
+"""GPU: the DCT upscale mode (FFTUP_FLAG_DCT, csrc/kernels_dct.hpp) against the fp64 matrix oracle of tests/dct_oracle.py, followed by
+oraclelib.sharpen, at the bars of tests/paritylib.py.  The amplitude-preserving image is y = upsq R, upsq as the plan holds it: at
+-p 2 rounded to binary16 (dct_oracle.upsq(u, half)).  The input is always an 8-bit frame.
 """
-import os
-import struct
 import subprocess
-import zlib
 
 import numpy as np
 import pytest
 
 import dct_oracle as D
 import oraclelib as O
+import paritylib as P
+from paritylib import CLI
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-30))
-
-
-def _m(tag, **vals):
-    print("MEASURED %s: %s" % (tag, "  ".join("%s %.3g" % kv for kv in vals.items())))
-
-
-def _frame(W, H, seed=0, dist="N"):
-    from vkresample_amd import synth
-    return synth.frame(seed, W, H, dist)
 
 
 def _run(rgb, u, precision, flags=0):
     import vkresample_amd as v
     H, W, _ = rgb.shape
-    with v.Upscaler(W, H, u, precision, 0.2, 0, flags | v.FLAG_DCT) as up:
-        up.upload_rgb8(rgb)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
-    return pre, out
-
-
-def _oracle(rgb, u, precision):
-    """(y, R): the oracle's y = upsq R from the plan's own input values, and R as the plan stores it"""
-    H, W, _ = rgb.shape
-    x = O.load_lut(precision)[np.transpose(rgb, (2, 0, 1))]
-    y = D.resample_planes(x, D.out_size(W, u), D.out_size(H, u))
-    R = y / D.upsq(u, precision == 2)
-    if precision == 2:
-        R = R.astype(np.float16).astype(np.float64)
-    return y, R
+    with v.Upscaler(W, H, u, precision, P.SHARPEN, 0, flags | v.FLAG_DCT) as up:
+        return P.run_uploaded(up, rgb)
 
 
 # (the 3*5*7 size: 840 = 2^3 3 5 7, 336 = 2^4 3 7 -- 1050 x 420 at -u 1.25, 2520 x 1008 at -u 3)
@@ -65,37 +29,14 @@ SIZES_FP32 = [(64, 32, 2.0), (96, 60, 1.5), (640, 480, 2.0), (1920, 1080, 2.0), 
 
 
 def _check(W, H, u, precision, fuse, seed, tag, pooled=None):
-    """one plan against the oracle at the bars above; `pooled`: a list that takes the -p 2 counts (differing, all) of R and of the
-    output in place of the two fraction bars (outputs of a few dozen values, tests/test_gpu_family_sweep.py)"""
+    """one plan against the oracle; `pooled`: see paritylib.assert_parity (tests/test_gpu_family_sweep.py)"""
     import vkresample_amd as v
-    rgb = _frame(W, H, seed=seed)
+    rgb = P.frame(W, H, seed=seed)
     pre, out = _run(rgb, u, precision, v.FLAG_FUSE_U8_LOAD if fuse else 0)
-    if precision == 0:
-        y, R = _oracle(rgb, u, 0)
-        assert pre.shape == y.shape
-        usq = D.upsq(u)
-        sh = O.sharpen(R, u, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(usq * pre, y), pre_max=np.abs(usq * pre - y).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max())
-        assert _rel_l2(usq * pre, y) <= 2e-6
-        assert np.abs(usq * pre - y).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-    else:
-        _, opre = _oracle(rgb, u, 2)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           out_diff_frac=(out != sh).mean())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        if pooled is None:
-            assert (pre != opre).mean() <= 0.01
-            assert (out != sh).mean() <= 0.02
-        else:
-            pooled.append((int((pre != opre).sum()), pre.size, int((out != sh).sum()), out.size))
+    x = O.load_lut(precision)[np.transpose(rgb, (2, 0, 1))]
+    y = D.resample_planes(x, D.out_size(W, u), D.out_size(H, u))
+    assert pre.shape == y.shape
+    P.assert_parity(tag, precision, pre, out, y, D.upsq(u, precision == 2), u, pooled=pooled)
     return pre, rgb
 
 
@@ -133,56 +74,16 @@ def test_dct_ramp_has_no_border_ringing():
             px, py = np.arange(uW) * W / uW, np.arange(uH) * H / uH
         ramp = 0.5 * px[None, :] / (W - 1) + 0.5 * py[:, None] / (H - 1)
         errs[name] = np.abs(y - ramp[None]).max()
-    _m("dct_ramp 128x64 u2", dct_max_err=errs["dct"], fft_max_err=errs["fft"])
+    P.measured("dct_ramp 128x64 u2", dct_max_err=errs["dct"], fft_max_err=errs["fft"])
     assert errs["dct"] <= 5e-3
     assert errs["fft"] > 0.1
-
-
-def _png_pixels(png, uW, uH):
-    """the RGB image of a PNG file of 8-bit RGB (zlib + the five row filters)"""
-    assert png[:8] == b"\x89PNG\r\n\x1a\n"
-    pos, idat = 8, b""
-    while pos < len(png):
-        n, = struct.unpack(">I", png[pos:pos + 4])
-        if png[pos + 4:pos + 8] == b"IDAT":
-            idat += png[pos + 8:pos + 8 + n]
-        pos += 12 + n
-    raw = zlib.decompress(idat)
-    stride = 3 * uW
-    assert len(raw) == uH * (stride + 1)
-    img = np.zeros((uH, stride), np.int64)
-    prev = np.zeros(stride, np.int64)
-    for r in range(uH):
-        ft = raw[r * (stride + 1)]
-        line = np.frombuffer(raw, np.uint8, stride, r * (stride + 1) + 1).astype(np.int64)
-        cur = np.zeros(stride, np.int64)
-        if ft == 0:
-            cur = line
-        elif ft == 2:
-            cur = (line + prev) & 255
-        else:
-            for i in range(stride):
-                a = cur[i - 3] if i >= 3 else 0
-                b = prev[i]
-                c = prev[i - 3] if i >= 3 else 0
-                if ft == 1:
-                    p = a
-                elif ft == 3:
-                    p = (a + b) >> 1
-                else:
-                    pa, pb, pc = abs(b - c), abs(a - c), abs(a + b - 2 * c)
-                    p = a if (pa <= pb and pa <= pc) else (b if pb <= pc else c)
-                cur[i] = (line[i] + p) & 255
-        img[r] = cur
-        prev = cur
-    return img.reshape(uH, uW, 3).astype(np.uint8)
 
 
 @pytest.mark.parametrize("W,H,u,precision", [(96, 60, 1.5, 0), (128, 64, 2.0, 2)])
 def test_dct_paths_give_identical_bytes(W, H, u, precision):
     """submit_rgb8, submit_png, OVERLAP_ITERATIONS and a ring of 4 compute the bytes of blocking upload / execute / download_rgb8"""
     import vkresample_amd as v
-    frames = [np.ascontiguousarray(_frame(W, H, seed=40 + k)) for k in range(4)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=40 + k)) for k in range(4)]
     want = []
     with v.Upscaler(W, H, u, precision, 0.2, 0, v.FLAG_DCT) as up:
         for f in frames:
@@ -207,7 +108,7 @@ def test_dct_paths_give_identical_bytes(W, H, u, precision):
         buf = np.empty(up.png_bound(), np.uint8)
         for k in (2, 0):
             n = up.wait_png(up.submit_png(frames[k]), buf)
-            assert np.array_equal(_png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
+            assert np.array_equal(P.png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
 
 
 def test_dct_plan_info_and_errors():
@@ -230,47 +131,37 @@ def test_dct_plan_info_and_errors():
     assert e.value.code == 2
 
 
-def _png_write(path, rgb):
-    from PIL import Image
-    Image.fromarray(rgb).save(path)
-
-
-def _png_read(path):
-    from PIL import Image
-    return np.asarray(Image.open(path).convert("RGB"))
-
-
 def test_dct_cli(tmp_path):
     """-dct gives the API's bytes, single-image and batched (-gpupng) mode, and not the FFT's"""
     import vkresample_amd as v
-    rgb = _frame(160, 96, seed=77)
+    rgb = P.frame(160, 96, seed=77)
     with v.Upscaler(160, 96, 2.0, 0, 0.2, 0, v.FLAG_DCT) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
         want = up.download_rgb8()
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
     outs = {}
     for tag, extra in (("dct", ["-dct"]), ("fft", [])):
         r = subprocess.run([CLI, "-i", "in.png", "-o", tag + ".png", "-u", "2", "-n", "1"] + extra, capture_output=True, text=True,
                            cwd=tmp_path, timeout=120)
         assert r.returncode == 0, r.stdout + r.stderr
-        outs[tag] = _png_read(tmp_path / (tag + ".png"))
+        outs[tag] = P.png_read(tmp_path / (tag + ".png"))
     assert np.array_equal(outs["dct"], want)
     assert not np.array_equal(outs["fft"], want)
     (tmp_path / "inp").mkdir()
     (tmp_path / "outp").mkdir()
-    _png_write(tmp_path / "inp" / "000001.png", rgb)
+    P.png_write(tmp_path / "inp" / "000001.png", rgb)
     r = subprocess.run([CLI, "-ifolder", "inp", "-ofolder", "outp", "-numfiles", "1", "-u", "2", "-dct", "-gpupng"], capture_output=True,
                        text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "outp" / "000001.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "outp" / "000001.png"), want)
 
 
 def test_dct_time_against_generic_fft():
     """2048x1024 -> 4096x2048 fp32: the DCT frame against the size-generic FFT frame, ordered iterations, alternating, device events"""
     import vkresample_amd as v
     W, H = 2048, 1024
-    rgb = _frame(W, H, seed=5)
+    rgb = P.frame(W, H, seed=5)
     with v.Upscaler(W, H, 2.0, 0, 0.2, 0, v.FLAG_DCT) as dct, v.Upscaler(W, H, 2.0, 0, 0.2, 0, v.FLAG_GENERIC_KERNELS) as fft:
         dct.upload_rgb8(rgb)
         fft.upload_rgb8(rgb)
@@ -282,6 +173,6 @@ def test_dct_time_against_generic_fft():
             tf.append(fft.execute(20))
         kd = dct.profile_kernels(20)
     d, f = float(np.median(td)), float(np.median(tf))
-    _m("dct_time 2048x1024 u2 fp32", dct_us=d * 1e3, fft_generic_us=f * 1e3, ratio=d / f,
-       dct_row_us=kd[0] * 1e3, dct_col_us=kd[1] * 1e3, idct_row_us=kd[2] * 1e3, sharpen_us=kd[3] * 1e3)
+    P.measured("dct_time 2048x1024 u2 fp32", dct_us=d * 1e3, fft_generic_us=f * 1e3, ratio=d / f,
+               dct_row_us=kd[0] * 1e3, dct_col_us=kd[1] * 1e3, idct_row_us=kd[2] * 1e3, sharpen_us=kd[3] * 1e3)
     assert d <= 2.0 * f

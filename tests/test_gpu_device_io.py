@@ -5,7 +5,7 @@ kernels are the same ones, only the pointers and strides they are launched with 
 strided pack) move or convert values exactly as the host path's copies and conversion launches do.  No tolerance is involved.
 
 Every output image sits in a buffer with 256-byte guard bands in front and behind, pre-filled with 0xA5 like all row and plane
-padding: after the run the pixels equal the host path's and every other byte is still 0xA5 (write containment).
+padding (tests/devimage.py): after the run the pixels equal the host path's and every other byte is still 0xA5 (write containment).
 
 Run directly (`python tests/test_gpu_device_io.py batch`) the file performs the batch check in a process of its own: the test that
 pins FFTUP_STREAMS=1 starts it that way, because the variable is read at plan creation of a fresh process."""
@@ -17,16 +17,13 @@ import sys
 import numpy as np
 import pytest
 
+from devimage import DTYPE, ESZ, FILL, GUARD, PLANAR, RGB8, Image, device_run
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 pytestmark = pytest.mark.gpu
-GUARD = 256
-FILL = 0xA5
-RGB8, PLANAR = 0, 1
-ESZ = {0: 4, 1: 8, 2: 2}
-DTYPE = {0: np.float32, 1: np.float64, 2: np.float16}
 
 
 def _make(key):
@@ -69,7 +66,7 @@ def _plan(key):
     return _plans[key]
 
 
-def _frame(up, fmt, seed):
+def _plan_frame(up, fmt, seed):
     """a W x H input frame: uint8 [H][W][3] or planes [3][H][W] of the plan's storage type with values in [0, 1)"""
     from vkresample_amd import synth
     if fmt == RGB8:
@@ -96,67 +93,10 @@ def _host(key, fmt, seed=7):
     k = (key, fmt, seed)
     if k not in _host_cache:
         up = _plan(key)
-        _host_cache[k] = _host_run(up, fmt, _frame(up, fmt, seed))
+        _host_cache[k] = _host_run(up, fmt, _plan_frame(up, fmt, seed))
         for a in _host_cache[k].values():
             a.flags.writeable = False
     return _host_cache[k]
-
-
-def _layout(fmt, w, h, esz, padded):
-    """(row bytes, row stride, plane stride, planes): dense, or rows padded by 5 bytes (RGB8) / 3 elements (PLANAR) and planes
-    by 2 rows"""
-    if fmt == RGB8:
-        return 3 * w, 3 * w + (5 if padded else 0), 0, 1
-    rs = (w + (3 if padded else 0)) * esz
-    return w * esz, rs, (h + (2 if padded else 0)) * rs, 3
-
-
-def _pixel_mask(total, base, planes, plane_stride, rows, row_stride, row_bytes):
-    m = np.zeros(total, dtype=bool)
-    for c in range(planes):
-        for y in range(rows):
-            o = base + c * plane_stride + y * row_stride
-            m[o:o + row_bytes] = True
-    return m
-
-
-class _Image:
-    """a device buffer holding one image at `base` bytes from its start, everything else 0xA5"""
-
-    def __init__(self, fmt, w, h, esz, padded=False, base=GUARD, frame=None):
-        import vkresample_amd as v
-        self.fmt = fmt
-        self.row_bytes, self.row_stride, self.plane_stride, self.planes = _layout(fmt, w, h, esz, padded)
-        extent = self.planes * self.plane_stride if fmt == PLANAR else h * self.row_stride
-        self.total = base + extent + GUARD
-        self.base = base
-        self.mask = _pixel_mask(self.total, base, self.planes, self.plane_stride, h, self.row_stride, self.row_bytes)
-        host = np.full(self.total, FILL, dtype=np.uint8)
-        if frame is not None:
-            host[self.mask] = np.ascontiguousarray(frame).reshape(-1).view(np.uint8)
-        self.buf = v.DeviceBuffer(self.total)
-        self.buf.upload(host)
-        self.image = v.DeviceImage(self.buf.ptr + base, fmt, self.row_stride, self.plane_stride)
-
-    def read(self, stream=None):
-        """-> (the pixels' bytes in dense order, True if every other byte is still 0xA5)"""
-        got = self.buf.download(stream=stream)
-        return got[self.mask], bool((got[~self.mask] == FILL).all())
-
-    def close(self):
-        self.buf.close()
-
-
-def _device_run(up, fmt_in, frame, fmt_out, in_padded=False, out_padded=False, in_base=GUARD, out_base=GUARD, stream=None):
-    esz = ESZ[up.precision]
-    src = _Image(fmt_in, up.width, up.height, esz, in_padded, in_base, frame)
-    dst = _Image(fmt_out, up.out_width, up.out_height, esz, out_padded, out_base)
-    try:
-        up.execute_device(src.image, dst.image, stream)
-        return dst.read(stream)
-    finally:
-        src.close()
-        dst.close()
 
 
 # ---------------------------------------------------------------- 1. equality over the plan kinds, dense, guard bands checked
@@ -167,15 +107,15 @@ def test_equals_host_path(key, fmt_in, fmt_out):
     import vkresample_amd as v
     up = _plan(key)
     want = _host(key, fmt_in)
-    frame = _frame(up, fmt_in, 7)
+    frame = _plan_frame(up, fmt_in, 7)
     if key == "u8store_p2":
         assert up.u8_store
     if up.u8_store and fmt_out == PLANAR:
         with pytest.raises(v.FftupError) as e:          # no planes on such a plan: the rule of fftup_download_planar
-            _device_run(up, fmt_in, frame, fmt_out)
+            device_run(up, fmt_in, frame, fmt_out)
         assert e.value.code == 1 and "FFTUP_FLAG_FUSE_U8_STORE" in str(e.value)
         return
-    got, clean = _device_run(up, fmt_in, frame, fmt_out)
+    got, clean = device_run(up, fmt_in, frame, fmt_out)
     assert np.array_equal(got, want[fmt_out])
     assert clean, "bytes outside the image were written"
 
@@ -187,7 +127,7 @@ def test_equals_host_path(key, fmt_in, fmt_out):
 def test_padded_rows_and_planes(key, fmt_in, fmt_out):
     up = _plan(key)
     want = _host(key, fmt_in)
-    got, clean = _device_run(up, fmt_in, _frame(up, fmt_in, 7), fmt_out, in_padded=True, out_padded=True)
+    got, clean = device_run(up, fmt_in, _plan_frame(up, fmt_in, 7), fmt_out, in_padded=True, out_padded=True)
     assert np.array_equal(got, want[fmt_out])
     assert clean, "row padding, plane padding or a guard band was written"
 
@@ -196,7 +136,7 @@ def test_padded_rows_of_a_fused_8bit_store():
     """FFTUP_FLAG_FUSE_U8_STORE with padded output rows: lane scratch + strided byte copy"""
     up = _plan("u8store_p2")
     want = _host("u8store_p2", RGB8)
-    got, clean = _device_run(up, RGB8, _frame(up, RGB8, 7), RGB8, in_padded=True, out_padded=True)
+    got, clean = device_run(up, RGB8, _plan_frame(up, RGB8, 7), RGB8, in_padded=True, out_padded=True)
     assert np.array_equal(got, want[RGB8]) and clean
 
 
@@ -207,10 +147,10 @@ def test_misaligned_planar_input(key, offset):
     """`data` one element behind a 256-byte boundary: read in place (the first kernels load single elements); one BYTE behind it:
     through the gather kernel into the lane's staging planes.  The same bytes as the aligned run's either way."""
     up = _plan(key)
-    frame = _frame(up, PLANAR, 7)
-    aligned, clean0 = _device_run(up, PLANAR, frame, PLANAR)
+    frame = _plan_frame(up, PLANAR, 7)
+    aligned, clean0 = device_run(up, PLANAR, frame, PLANAR)
     off = ESZ[up.precision] if offset == "element" else 1
-    got, clean = _device_run(up, PLANAR, frame, PLANAR, in_base=GUARD + off)
+    got, clean = device_run(up, PLANAR, frame, PLANAR, in_base=GUARD + off)
     assert np.array_equal(got, aligned) and np.array_equal(got, _host(key, PLANAR)[PLANAR])
     assert clean0 and clean
 
@@ -223,7 +163,7 @@ def test_misaligned_output(key, offset):
     up = _plan(key)
     fmt = RGB8 if up.u8_store else PLANAR
     off = ESZ[up.precision] if offset == "element" else 1
-    got, clean = _device_run(up, RGB8, _frame(up, RGB8, 7), fmt, out_base=GUARD + off)
+    got, clean = device_run(up, RGB8, _plan_frame(up, RGB8, 7), fmt, out_base=GUARD + off)
     assert np.array_equal(got, _host(key, RGB8)[fmt]) and clean
 
 
@@ -232,11 +172,11 @@ def _batch_check():
     """five distinct frames through one call on a ring = 1 plan: each output equals that frame's own host-path result"""
     import vkresample_amd as v
     with v.Upscaler(64, 32, 2.0, 0, ring=1) as up:
-        frames = [_frame(up, RGB8, 20 + i) for i in range(5)]
+        frames = [_plan_frame(up, RGB8, 20 + i) for i in range(5)]
         want = [_host_run(up, RGB8, f)[PLANAR] for f in frames]
         assert len({w.tobytes() for w in want}) == 5
-        src = [_Image(RGB8, 64, 32, 4, frame=f) for f in frames]
-        dst = [_Image(PLANAR, 128, 64, 4) for _ in frames]
+        src = [Image(RGB8, 64, 32, 4, frame=f) for f in frames]
+        dst = [Image(PLANAR, 128, 64, 4) for _ in frames]
         try:
             up.execute_device([s.image for s in src], [d.image for d in dst])
             for d, w in zip(dst, want):
@@ -267,16 +207,16 @@ def test_two_plans_chained_on_one_stream(own_stream):
     """A: 64x32 -> 128x64, B: 128x64 -> 64x32 (downscale), B reading what A writes, with nothing but the stream between them"""
     import vkresample_amd as v
     A, B = _plan("default"), _plan("down")
-    x = _frame(A, PLANAR, 31)
+    x = _plan_frame(A, PLANAR, 31)
     A.upload_planar(x)
     A.execute(1)
     B.upload_planar(A.download_planar())
     B.execute(1)
     want = B.download_planar().reshape(-1).view(np.uint8)
     s = v.Stream() if own_stream else None
-    src = _Image(PLANAR, 64, 32, 4)
-    mid = _Image(PLANAR, 128, 64, 4)
-    dst = _Image(PLANAR, 64, 32, 4)
+    src = Image(PLANAR, 64, 32, 4)
+    mid = Image(PLANAR, 128, 64, 4)
+    dst = Image(PLANAR, 64, 32, 4)
     try:
         host = np.full(src.total, FILL, dtype=np.uint8)
         host[src.mask] = x.reshape(-1).view(np.uint8)
@@ -296,10 +236,10 @@ def test_two_plans_chained_on_one_stream(own_stream):
 def test_invalid_descriptors_are_refused_before_any_launch():
     import vkresample_amd as v
     up = _plan("default")
-    frame = _frame(up, RGB8, 7)
-    src = _Image(RGB8, 64, 32, 4, frame=frame)
-    srcp = _Image(PLANAR, 64, 32, 4, frame=_frame(up, PLANAR, 7))
-    dst = _Image(PLANAR, 128, 64, 4)
+    frame = _plan_frame(up, RGB8, 7)
+    src = Image(RGB8, 64, 32, 4, frame=frame)
+    srcp = Image(PLANAR, 64, 32, 4, frame=_plan_frame(up, PLANAR, 7))
+    dst = Image(PLANAR, 128, 64, 4)
     host_rgb = np.ascontiguousarray(frame)
     good_in, good_out = src.image, dst.image
     cases = [
@@ -331,7 +271,7 @@ def test_invalid_descriptors_are_refused_before_any_launch():
 # ---------------------------------------------------------------- 7. the ring slots are neither read nor written
 def test_slots_untouched():
     up = _plan("default")
-    f0, f1 = _frame(up, RGB8, 40), _frame(up, RGB8, 41)
+    f0, f1 = _plan_frame(up, RGB8, 40), _plan_frame(up, RGB8, 41)
     up.upload_rgb8(f0)
     up.execute(1)
     planes, word_sum = up.download_planar().copy(), up.output_checksum(0)
@@ -339,7 +279,7 @@ def test_slots_untouched():
     up.upload_rgb8(f0)
     up.execute(1)
     assert np.array_equal(up.download_planar(), planes)
-    got, clean = _device_run(up, RGB8, f1, PLANAR)
+    got, clean = device_run(up, RGB8, f1, PLANAR)
     assert np.array_equal(got, other) and clean and not np.array_equal(got, planes.reshape(-1).view(np.uint8))
     assert np.array_equal(up.download_planar(0), planes) and up.output_checksum(0) == word_sum
     up.execute(1)                                          # ... and the input slot still holds f0
@@ -376,7 +316,7 @@ def _fresh(precision, flags, seed, planar=False):
     if k not in _fresh_cache:
         with _fs_plan(precision, flags | v.FLAG_OVERLAP_ITERATIONS, ring=1) as up:
             if planar:
-                up.upload_planar(_frame(up, PLANAR, seed))
+                up.upload_planar(_plan_frame(up, PLANAR, seed))
             else:
                 up.upload_rgb8(_fs_frame(seed))
             up.execute(1)
@@ -451,7 +391,7 @@ def test_ring_run_device_frame_ring_run_leave_nothing_behind(precision):
     with _fs_plan(precision) as up:
         _ring_run_ab(up)
         first = [(up.download_planar(s), up.output_checksum(s)) for s in range(2)]
-        got, clean = _device_run(up, PLANAR, _frame(up, PLANAR, SEED_C), RGB8, out_padded=True, in_base=GUARD + 1)
+        got, clean = device_run(up, PLANAR, _plan_frame(up, PLANAR, SEED_C), RGB8, out_padded=True, in_base=GUARD + 1)
         assert np.array_equal(got, c["rgb8"].reshape(-1)) and clean
         up.execute_ring(2)
         for s in range(2):

@@ -1,40 +1,17 @@
 """GPU: the downscale mode (FFTUP_FLAG_DOWNSCALE, csrc/kernels_downscale.hpp; with FFTUP_FLAG_DCT csrc/kernels_dct.hpp) against
-the fp64 oracle of tests/downscale_oracle.py.
-
-Bars: those of tests/test_gpu_dct.py.  fp32: the pre-sharpen image y within relative L2 2e-6 and max 1e-5 of full scale; the
-sharpened output against oraclelib.sharpen applied to the oracle's R within relative L2 5e-6 and max 2e-5.  fp16 (-p 2): R
-within one binary16 ulp of the oracle's own binary16 value and different from it in <= 1 % of the pixels; output relative L2
-<= 3.5e-4, different in <= 2 %, max 8e-3.  The last output row is compared too: its reads
-past the end of a plane, undefined in the reference (quirk B5), are defined here as "same column, last written row"
-(oracle/fftup_oracle.c), and the HIP path is held to that definition.
+the fp64 oracle of tests/downscale_oracle.py, followed by oraclelib.sharpen, at the bars of tests/paritylib.py.
 FFT mode: y = R (uW uH) / (W H); DCT mode: y = upsq R.
 """
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import downscale_oracle as S
-import oraclelib as O
-from test_gpu_dct import _png_pixels, _png_read, _png_write
+import paritylib as P
+from paritylib import CLI
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-30))
-
-
-def _m(tag, **vals):
-    print("MEASURED %s: %s" % (tag, "  ".join("%s %.3g" % kv for kv in vals.items())))
-
-
-def _frame(W, H, seed=0, dist="N"):
-    from vkresample_amd import synth
-    return synth.frame(seed, W, H, dist)
 
 
 def _scale(W, H, u, dct, half=False):
@@ -47,61 +24,19 @@ def _scale(W, H, u, dct, half=False):
 
 def _run(W, H, u, precision, flags, rgb=None, planes=None):
     import vkresample_amd as v
-    with v.Upscaler(W, H, u, precision, 0.2, 0, flags | v.FLAG_DOWNSCALE) as up:
-        if rgb is not None:
-            up.upload_rgb8(rgb)
-        else:
-            up.upload_planar(planes)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
-    return pre, out
-
-
-def _inputs(W, H, precision, uint8, seed):
-    """(rgb, planes, x): what is uploaded and the values the plan computes on.  Planar input: a natural-like frame as floats
-    (x / 255 plus a little noise below one 8-bit step), in the plan's storage type -- the bars are those of natural frames"""
-    rgb = _frame(W, H, seed=seed)
-    if uint8:
-        return rgb, None, O.load_lut(precision)[np.transpose(rgb, (2, 0, 1))]
-    x = np.transpose(rgb, (2, 0, 1)) / 255.0 + np.random.RandomState(seed).rand(3, H, W) / 512.0
-    planes = x.astype(np.float16 if precision == 2 else np.float32)
-    return None, planes, planes.astype(np.float64)
+    with v.Upscaler(W, H, u, precision, P.SHARPEN, 0, flags | v.FLAG_DOWNSCALE) as up:
+        return P.run_uploaded(up, rgb, planes)
 
 
 def _check(W, H, u, precision, dct, uint8, seed, tag, pooled=None):
     import vkresample_amd as v
-    rgb, planes, x = _inputs(W, H, precision, uint8, seed)
+    rgb, planes, x = P.inputs(W, H, precision, uint8, seed)
     flags = (v.FLAG_DCT if dct else 0) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0)
     pre, out = _run(W, H, u, precision, flags, rgb, planes)
     uW, uH = S.out_size(W, u), S.out_size(H, u)
-    sc = _scale(W, H, u, dct, precision == 2)
     y = S.dct_down_planes(x, uW, uH) if dct else S.fft_down_planes(x, uW, uH)
     assert pre.shape == y.shape == (3, uH, uW)
-    R = y / sc
-    if precision == 0:
-        sh = O.sharpen(R, u, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(sc * pre, y), pre_max=np.abs(sc * pre - y).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max())
-        assert _rel_l2(sc * pre, y) <= 2e-6
-        assert np.abs(sc * pre - y).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           out_diff_frac=(out != sh).mean())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        if pooled is None:
-            assert (pre != opre).mean() <= 0.01
-            assert (out != sh).mean() <= 0.02
-        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
-            pooled.append((int((pre != opre).sum()), pre.size, int((out != sh).sum()), out.size))
+    P.assert_parity(tag, precision, pre, out, y, _scale(W, H, u, dct, precision == 2), u, pooled=pooled)
 
 
 # 16x512 -u 0.5: a thin frame whose column pass (512 points, tiles of 8) needs 69 648 bytes of dynamic LDS -- above the 64 KB a
@@ -140,8 +75,8 @@ def test_constant_frame_stays_constant():
     import vkresample_amd as v
     for flags in (0, v.FLAG_DCT):
         y = _pre_y(1000, 800, 0.8, np.full((3, 800, 1000), 0.37), flags)
-        _m("down_const flags%d" % flags, max_err=np.abs(y - 0.37).max())
-        assert np.abs(y - 0.37).max() <= 1e-5
+        P.measured("down_const flags%d" % flags, max_err=np.abs(y - 0.37).max())
+        assert np.abs(y - 0.37).max() <= P.FP32_PRE_MAX
 
 
 def test_band_limited_frame_decimates():
@@ -157,8 +92,8 @@ def test_band_limited_frame_decimates():
             x += 0.04 * np.cos(2 * np.pi * (ky * yy / H + kx * xx / W) + rng.rand() * 6.28)
         x = x.astype(np.float32).astype(np.float64)
         y = _pre_y(W, H, 1.0 / d, x)
-        _m("down_bandlimited d%d" % d, max_err=np.abs(y - x[:, ::d, ::d]).max())
-        assert np.abs(y - x[:, ::d, ::d]).max() <= 1e-5
+        P.measured("down_bandlimited d%d" % d, max_err=np.abs(y - x[:, ::d, ::d]).max())
+        assert np.abs(y - x[:, ::d, ::d]).max() <= P.FP32_PRE_MAX
 
 
 def test_content_above_new_nyquist_vanishes():
@@ -167,8 +102,8 @@ def test_content_above_new_nyquist_vanishes():
     yy, xx = np.mgrid[0:H, 0:W]
     x = 0.5 + 0.2 * np.cos(2 * np.pi * 0.375 * xx + 0.3) + 0.2 * np.cos(2 * np.pi * 0.375 * yy + 1.1)
     y = _pre_y(W, H, 0.5, np.broadcast_to(x, (3, H, W)))
-    _m("down_antialias", max_err=np.abs(y - 0.5).max())
-    assert np.abs(y - 0.5).max() <= 1e-5
+    P.measured("down_antialias", max_err=np.abs(y - 0.5).max())
+    assert np.abs(y - 0.5).max() <= P.FP32_PRE_MAX
 
 
 def test_fft_up_then_down_returns_the_frame():
@@ -186,8 +121,8 @@ def test_fft_up_then_down_returns_the_frame():
         up.execute(1)
         yup = up.download_presharpen() * np.float32(S.upsq(2.0))
     y = _pre_y(2 * W, 2 * H, 0.5, yup)
-    _m("down_fft_roundtrip", max_err=np.abs(y - x).max())
-    assert np.abs(y - x).max() <= 1e-5
+    P.measured("down_fft_roundtrip", max_err=np.abs(y - x).max())
+    assert np.abs(y - x).max() <= P.FP32_PRE_MAX
 
 
 def test_dct_up_then_down_returns_the_frame():
@@ -199,8 +134,8 @@ def test_dct_up_then_down_returns_the_frame():
         up.execute(1)
         yup = up.download_presharpen() * np.float32(S.upsq(2.0))
     y = _pre_y(2 * W, 2 * H, 0.5, yup, v.FLAG_DCT)
-    _m("down_dct_roundtrip", max_err=np.abs(y - x).max())
-    assert np.abs(y - x).max() <= 1e-5
+    P.measured("down_dct_roundtrip", max_err=np.abs(y - x).max())
+    assert np.abs(y - x).max() <= P.FP32_PRE_MAX
 
 
 @pytest.mark.parametrize("W,H,u,precision,flags", [(192, 120, 0.5, 0, 0), (256, 128, 0.75, 2, 0), (160, 96, 0.5, 0, 256)])
@@ -209,7 +144,7 @@ def test_down_paths_give_identical_bytes(W, H, u, precision, flags):
     with equal output checksums"""
     import vkresample_amd as v
     flags |= v.FLAG_DOWNSCALE
-    frames = [np.ascontiguousarray(_frame(W, H, seed=60 + k)) for k in range(4)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=60 + k)) for k in range(4)]
     want, sums = [], []
     with v.Upscaler(W, H, u, precision, 0.2, 0, flags) as up:
         for f in frames:
@@ -237,32 +172,32 @@ def test_down_paths_give_identical_bytes(W, H, u, precision, flags):
         buf = np.empty(up.png_bound(), np.uint8)
         for k in (2, 0):
             n = up.wait_png(up.submit_png(frames[k]), buf)
-            assert np.array_equal(_png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
+            assert np.array_equal(P.png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
 
 
 def test_down_cli(tmp_path):
     """-u 1/2 -downscale gives the API's bytes, single-image and batched (-gpupng); without -downscale the CLI refuses"""
     import vkresample_amd as v
-    rgb = _frame(320, 192, seed=78)
+    rgb = P.frame(320, 192, seed=78)
     with v.Upscaler(320, 192, 0.5, 0, 0.2, 0, v.FLAG_DOWNSCALE) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
         want = up.download_rgb8()
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
     r = subprocess.run([CLI, "-i", "in.png", "-o", "down.png", "-u", "1/2", "-n", "1", "-downscale"], capture_output=True, text=True,
                        cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "down.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "down.png"), want)
     r = subprocess.run([CLI, "-i", "in.png", "-o", "bad.png", "-u", "0.5", "-n", "1"], capture_output=True, text=True,
                        cwd=tmp_path, timeout=120)
     assert r.returncode != 0 and not (tmp_path / "bad.png").exists()
     (tmp_path / "inp").mkdir()
     (tmp_path / "outp").mkdir()
-    _png_write(tmp_path / "inp" / "000001.png", rgb)
+    P.png_write(tmp_path / "inp" / "000001.png", rgb)
     r = subprocess.run([CLI, "-ifolder", "inp", "-ofolder", "outp", "-numfiles", "1", "-u", "1/2", "-downscale", "-gpupng"],
                        capture_output=True, text=True, cwd=tmp_path, timeout=120)
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "outp" / "000001.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "outp" / "000001.png"), want)
 
 
 def test_down_plan_info_and_errors():

@@ -1,13 +1,7 @@
 """GPU: fftup_plan_create_size (Upscaler.to_size) -- an exact output size, one factor per axis, optional alignment of the pixel
 centres -- against the fp64 statement of the rule, tests/exactsize_oracle.py, followed by oraclelib.sharpen with the effective
-factor u_e = (float)sqrt(uW uH / (W H)) (quirks B4, B5; B1-B3 do not apply to these plans).
-
-Bars: the project's, as stated in tests/test_gpu_oddsize.py.  fp32: the amplitude-preserving image sc * pre, sc = uW uH / (W H),
-within relative L2 2e-6 and max 1e-5 of the oracle's y; the sharpened output against oraclelib.sharpen applied to the oracle's R
-within relative L2 5e-6 and max 2e-5.  fp16 (-p 2): R within one binary16 ulp of the oracle's own binary16 value and different from
-it in <= 1 % of the pixels; output relative L2 <= 3.5e-4, different in <= 2 %, max 8e-3.  The last output row is compared too: its reads
-past the end of a plane, undefined in the reference (quirk B5), are defined here as "same column, last written row"
-(oracle/fftup_oracle.c), and the HIP path is held to that definition.
+factor u_e = (float)sqrt(uW uH / (W H)) (quirks B4, B5; B1-B3 do not apply to these plans), at the bars of tests/paritylib.py.  The
+amplitude-preserving image is sc * R, sc = uW uH / (W H).
 
 The small cases are chosen so that each branch of the bin map is the only thing that can go wrong; each runs at both alignments,
 -p 0 and -p 2, planar and fused-uint8 input.  One workload-sized case runs in the default run (1366x768 -> 1920x1080, -p 0, centres);
@@ -20,12 +14,10 @@ import pytest
 
 import exactsize_oracle as E
 import oraclelib as O
-from test_gpu_dct import _png_pixels, _png_read, _png_write
-from test_gpu_oddsize import _frame, _inputs, _m, _rel_l2, _word_sum
+import paritylib as P
+from paritylib import CLI
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 BIG = os.environ.get("FFTUP_BIG_TESTS", "0") != "0"
 
 # 50x32 -> 32x50: all even, rows folded, columns split (the mixed case); 40x30 -> 25x48: odd output row length, mixed; 64x48 -> 64x72:
@@ -39,14 +31,8 @@ def _flags(v, extra):
 
 def _run(W, H, uW, uH, precision, flags, align, rgb=None, planes=None):
     import vkresample_amd as v
-    with v.Upscaler.to_size(W, H, uW, uH, precision, 0.2, 0, flags, align=align) as up:
-        if rgb is not None:
-            up.upload_rgb8(rgb)
-        else:
-            up.upload_planar(planes)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
+    with v.Upscaler.to_size(W, H, uW, uH, precision, P.SHARPEN, 0, flags, align=align) as up:
+        pre, out = P.run_uploaded(up, rgb, planes)
         names, desc = up.kernel_names, up.description
         assert (up.out_width, up.out_height) == (uW, uH)
         assert not up.tuned and not up.u8_store and up.num_kernels == 4
@@ -55,7 +41,7 @@ def _run(W, H, uW, uH, precision, flags, align, rgb=None, planes=None):
 
 def _check(W, H, uW, uH, precision, extra, align, uint8, seed, tag, pooled=None):
     import vkresample_amd as v
-    rgb, planes, x = _inputs(W, H, precision, uint8, seed)
+    rgb, planes, x = P.inputs(W, H, precision, uint8, seed)
     pre, out, names, desc = _run(W, H, uW, uH, precision, _flags(v, extra) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0), align, rgb, planes)
     assert all("_odd" in n for n in names[:3]) and names[3] == "sharpen", names
     assert "rows %d->%d" % (W, uW) in desc and "columns %d->%d" % (H, uH) in desc, desc
@@ -64,30 +50,7 @@ def _check(W, H, uW, uH, precision, extra, align, uint8, seed, tag, pooled=None)
     sc = uW * uH / (W * H)
     u_e = E.effective_factor(W, H, uW, uH)
     assert pre.shape == R.shape == (3, uH, uW)
-    y = sc * R
-    if precision == 0:
-        sh = O.sharpen(R, u_e, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(sc * pre, y), pre_max=np.abs(sc * pre - y).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max())
-        assert _rel_l2(sc * pre, y) <= 2e-6
-        assert np.abs(sc * pre - y).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u_e, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           out_diff_frac=(out != sh).mean())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        if pooled is None:
-            assert (pre != opre).mean() <= 0.01
-            assert (out != sh).mean() <= 0.02
-        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
-            pooled.append((int((pre != opre).sum()), pre.size, int((out != sh).sum()), out.size))
+    P.assert_parity(tag, precision, pre, out, sc * R, sc, u_e, pooled=pooled)
     return pre, x
 
 
@@ -100,8 +63,7 @@ def test_exactsize_parity(W, H, uW, uH, extra, align, precision, uint8):
                     "exactsize p%d %dx%d->%dx%d a%d %s u8%d" % (precision, W, H, uW, uH, align, extra, uint8))
     if (W, H) == (uW, uH) and precision == 0:
         # the identity at both alignments (the oracle reproduces the input to 1e-15)
-        _m("exactsize identity %dx%d a%d" % (W, H, align), max_err=np.abs(pre - x).max(), l2=_rel_l2(pre, x))
-        assert _rel_l2(pre, x) <= 2e-6 and np.abs(pre - x).max() <= 1e-5
+        P.assert_identity("exactsize identity %dx%d a%d" % (W, H, align), pre, x)
 
 
 @pytest.mark.parametrize("precision", [0, 2] if BIG else [0])
@@ -121,9 +83,9 @@ def test_cosine_comes_back_at_the_centre_aligned_positions(W, H, uW, uH, extra):
         x = np.ascontiguousarray(np.broadcast_to(row, (3, H, W)).astype(np.float32))
         pre, _, _, _ = _run(W, H, uW, uH, 0, _flags(v, extra), E.ALIGN_CENTRE, planes=x)
         want = np.broadcast_to(0.5 + a * np.cos(2 * np.pi * k * pos / W + 0.4), (3, uH, uW))
-        _m("exactsize cosine %d->%d k=%d" % (W, uW, k), max_err=np.abs(sc * pre - want).max(), l2=_rel_l2(sc * pre, want))
-        assert _rel_l2(sc * pre, want) <= 2e-6
-        assert np.abs(sc * pre - want).max() <= 1e-5
+        P.measured("exactsize cosine %d->%d k=%d" % (W, uW, k), max_err=np.abs(sc * pre - want).max(), l2=P.rel_l2(sc * pre, want))
+        assert P.rel_l2(sc * pre, want) <= P.FP32_PRE_L2
+        assert np.abs(sc * pre - want).max() <= P.FP32_PRE_MAX
 
 
 @pytest.mark.parametrize("W,H,uW,uH,extra", [(46, 22, 70, 30, "any"), (50, 32, 32, 50, ""), (40, 30, 25, 48, "")])
@@ -131,20 +93,20 @@ def test_mirroring_the_input_mirrors_the_output(W, H, uW, uH, extra):
     """centre alignment commutes with mirroring both axes (corner alignment does not: tests/test_exactsize_oracle.py); compared on
     the pre-sharpen image, whose sharpen pass has a direction of its own (quirk B5)"""
     import vkresample_amd as v
-    _, planes, _ = _inputs(W, H, 0, False, 21)
+    _, planes, _ = P.inputs(W, H, 0, False, 21)
     sc = uW * uH / (W * H)
     a, _, _, _ = _run(W, H, uW, uH, 0, _flags(v, extra), E.ALIGN_CENTRE, planes=np.ascontiguousarray(planes[:, ::-1, ::-1]))
     b, _, _, _ = _run(W, H, uW, uH, 0, _flags(v, extra), E.ALIGN_CENTRE, planes=planes)
     b = b[:, ::-1, ::-1]
-    _m("exactsize mirror %dx%d->%dx%d" % (W, H, uW, uH), max_err=sc * np.abs(a - b).max(), l2=_rel_l2(a, b))
-    assert _rel_l2(a, b) <= 2e-6 and sc * np.abs(a - b).max() <= 1e-5
+    P.measured("exactsize mirror %dx%d->%dx%d" % (W, H, uW, uH), max_err=sc * np.abs(a - b).max(), l2=P.rel_l2(a, b))
+    assert P.rel_l2(a, b) <= P.FP32_PRE_L2 and sc * np.abs(a - b).max() <= P.FP32_PRE_MAX
 
 
 @pytest.mark.parametrize("precision", [0, 2])
 def test_corner_aligned_u2_is_the_oddsize_plan(precision):
     """1215x675 -> 2430x1350, corners: u_e = 2 exactly, the same kernels without a phase table -- the bytes of FLAG_ODD_SIZE -u 2"""
     import vkresample_amd as v
-    rgb = _frame(1215, 675, seed=31)
+    rgb = P.frame(1215, 675, seed=31)
     got = []
     for make in (lambda: v.Upscaler(1215, 675, 2.0, precision, 0.2, 0, v.FLAG_ODD_SIZE),
                  lambda: v.Upscaler.to_size(1215, 675, 2430, 1350, precision, 0.2, 0, 0, align=E.ALIGN_CORNER)):
@@ -155,7 +117,7 @@ def test_corner_aligned_u2_is_the_oddsize_plan(precision):
                         up.kernel_min_bytes))
     assert got[0][1:] == got[1][1:]
     assert got[0][0] == got[1][0]
-    assert got[0][1] == _word_sum(got[0][0])
+    assert got[0][1] == P.word_sum(got[0][0])
 
 
 def test_existing_plans_keep_their_results():
@@ -165,7 +127,7 @@ def test_existing_plans_keep_their_results():
     from test_gpu_oddsize import _check as odd_check
     odd_check(45, 21, 2.0, 0, "", False, 66, "oddsize p0 45x21 u2 (beside exact-size plans)")
     odd_check(125, 75, 0.6, 2, "down", True, 202, "oddsize p2 125x75 u0.6 down (beside exact-size plans)")
-    rgb = _frame(240, 126, seed=7)
+    rgb = P.frame(240, 126, seed=7)
     with v.Upscaler(240, 126, 2.0, 0, 0.2, 0, v.FLAG_GENERIC_KERNELS) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
@@ -173,10 +135,10 @@ def test_existing_plans_keep_their_results():
         out = up.download_planar().astype(np.float64)
         assert up.kernel_names == ["row_r2c", "col_fwd_pad_inv", "row_c2r", "sharpen"] and "exact" not in up.description
     opre, oout, _ = O.upscale_rgb8(rgb, 2.0, 0, 0.2)
-    _m("even plan 240x126 u2", pre_l2=_rel_l2(pre, opre), pre_max=4 * np.abs(pre - opre).max(), out_l2=_rel_l2(out, oout),
-       out_max=np.abs(out - oout).max())
-    assert _rel_l2(pre, opre) <= 2e-6 and 4 * np.abs(pre - opre).max() <= 1e-5
-    assert _rel_l2(out, oout) <= 5e-6 and np.abs(out - oout).max() <= 2e-5
+    P.measured("even plan 240x126 u2", pre_l2=P.rel_l2(pre, opre), pre_max=4 * np.abs(pre - opre).max(), out_l2=P.rel_l2(out, oout),
+               out_max=np.abs(out - oout).max())
+    assert P.rel_l2(pre, opre) <= P.FP32_PRE_L2 and 4 * np.abs(pre - opre).max() <= P.FP32_PRE_MAX
+    assert P.rel_l2(out, oout) <= P.FP32_OUT_L2 and np.abs(out - oout).max() <= P.FP32_OUT_MAX
 
 
 @pytest.mark.parametrize("precision", [0, 2])
@@ -185,7 +147,7 @@ def test_every_execution_path_gives_the_same_bytes(precision):
     download_rgb8, FLAG_OVERLAP_ITERATIONS against ordered iterations, the checksum equal to the sum of the words"""
     import vkresample_amd as v
     W, H, uW, uH, al = 50, 32, 32, 50, E.ALIGN_CENTRE
-    frames = [np.ascontiguousarray(_frame(W, H, seed=60 + k)) for k in range(3)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=60 + k)) for k in range(3)]
     want, planes, sums = [], [], []
     with v.Upscaler.to_size(W, H, uW, uH, precision, 0.2, 0, 0, align=al) as up:
         for f in frames:
@@ -194,7 +156,7 @@ def test_every_execution_path_gives_the_same_bytes(precision):
             want.append(up.download_rgb8())
             planes.append(up.download_planar().tobytes())
             sums.append(up.output_checksum())
-            assert sums[-1] == _word_sum(planes[-1])
+            assert sums[-1] == P.word_sum(planes[-1])
         ms = up.profile_kernels(2)
         assert len(ms) >= 4 and all(t > 0 for t in list(ms)[:4])
     with v.Upscaler.to_size(W, H, uW, uH, precision, 0.2, 0, v.FLAG_OVERLAP_ITERATIONS, align=al) as up:
@@ -221,7 +183,7 @@ def test_every_execution_path_gives_the_same_bytes(precision):
         buf = np.empty(up.png_bound(), np.uint8)
         for k in (2, 0):
             n = up.wait_png(up.submit_png(frames[k]), buf)
-            assert np.array_equal(_png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
+            assert np.array_equal(P.png_pixels(bytes(buf[:n]), uW, uH), want[k]), k
 
 
 def test_plan_info_and_errors():
@@ -252,7 +214,7 @@ def test_exactsize_cli(tmp_path):
     """-size 70x30 -centres -anysize on a 46x22 PNG gives the API's pixels, single-image and batched (host and -gpupng encoders); -size
     with -u and -centres without -size exit 1 with a message and write nothing"""
     import vkresample_amd as v
-    rgb = _frame(46, 22, seed=78)
+    rgb = P.frame(46, 22, seed=78)
     with v.Upscaler.to_size(46, 22, 70, 30, 0, 0.2, 0, v.FLAG_ANY_SIZE, align=E.ALIGN_CENTRE) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
@@ -262,7 +224,7 @@ def test_exactsize_cli(tmp_path):
         up.execute(1)
         corner = up.download_rgb8()
     assert not np.array_equal(want, corner)
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
 
     def cli(*args):
         return subprocess.run([CLI] + list(args), capture_output=True, text=True, cwd=tmp_path, timeout=120)
@@ -270,10 +232,10 @@ def test_exactsize_cli(tmp_path):
     r = cli("-i", "in.png", "-o", "out.png", "-size", "70x30", "-centres", "-anysize", "-n", "1")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "46x22 to 70x30" in r.stdout
-    assert np.array_equal(_png_read(tmp_path / "out.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "out.png"), want)
     r = cli("-i", "in.png", "-o", "corner.png", "-size", "70x30", "-anysize")
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "corner.png"), corner)
+    assert np.array_equal(P.png_read(tmp_path / "corner.png"), corner)
     r = cli("-i", "in.png", "-o", "bad.png", "-size", "70x30", "-u", "2", "-anysize")
     assert r.returncode == 1 and "-u" in r.stdout and not (tmp_path / "bad.png").exists()
     r = cli("-i", "in.png", "-o", "bad.png", "-u", "2", "-centres", "-anysize")
@@ -285,8 +247,8 @@ def test_exactsize_cli(tmp_path):
         outp = tmp_path / ("outp%d" % k)
         outp.mkdir()
         for n in (1, 2):
-            _png_write(tmp_path / "inp" / ("%06d.png" % n), rgb)
+            P.png_write(tmp_path / "inp" / ("%06d.png" % n), rgb)
         r = cli("-ifolder", "inp", "-ofolder", outp.name, "-numfiles", "2", "-size", "70x30", "-centres", "-anysize", *extra)
         assert r.returncode == 0, r.stdout + r.stderr
         for n in (1, 2):
-            assert np.array_equal(_png_read(outp / ("%06d.png" % n)), want), (extra, n)
+            assert np.array_equal(P.png_read(outp / ("%06d.png" % n)), want), (extra, n)

@@ -1,7 +1,6 @@
 """GPU: seeded sweeps over the plan families added after tests/test_gpu_sweep.py -- exact-size, odd-size, any-size, downscale (FFT
 and DCT), DCT upscale and view plans -- each case against its family's own oracle through its family's own _check, at the
-project's bars exactly as the docstrings of tests/test_gpu_exactsize.py, test_gpu_oddsize.py, test_gpu_anysize.py,
-test_gpu_downscale.py, test_gpu_dct.py and test_gpu_view.py state them.  No bar is stated or widened here.
+project's bars exactly as tests/paritylib.py states them.  No bar is stated or widened here.
 
 The cases come from tests/family_sweep_cases.py: per arm a forced part (the strata: lengths of 2 and 3, every parity class of an
 axis at both alignments, folded and split Nyquist bins, Bluestein lengths of 2N - 1, column tile widths 4, 2 and 1, a column pass
@@ -15,10 +14,10 @@ Precision (-p 0, -p 2) and input kind (planar, fused uint8) are dealt per case, 
 a case whose output has fewer values than the smallest case of its family's existing -p 2 parity list (TINY below, read off those
 lists) runs -p 0 in the parametrized test and -p 2 in one pooled test per arm, which asserts the one-ulp bound, the output's L2 and
 max bars per case and the two fraction bars on the pooled counts.  M = N / -u 1 cases also meet the identity bar of the family
-modules (relative L2 2e-6, max 1e-5 against the input).
+modules (paritylib.assert_identity).
 
 Worst values measured on an MI355X, default run / one-off run of 100 cases per arm (profiles/family_sweep_long.txt; default seed).
--p 0, bars 2e-6, 1e-5, 5e-6, 2e-5; identity bars 2e-6, 1e-5:
+-p 0 (bars: paritylib.FP32_*, in the columns' order; the identity's are the first two):
     arm    pre_l2            pre_max           out_l2            out_max           identity l2, max (the larger run)
     exact  2.9e-7 / 2.9e-7   7.1e-7 / 8.9e-7   7.2e-7 / 7.3e-7   2.1e-6 / 2.4e-6   2.7e-7, 6.6e-7
     odd    2.7e-7 / 3.3e-7   6.0e-7 / 7.9e-7   6.8e-7 / 7.6e-7   1.8e-6 / 2.4e-6   (no -u 1 among the factors)
@@ -26,7 +25,7 @@ Worst values measured on an MI355X, default run / one-off run of 100 cases per a
     down   1.6e-7 / 1.8e-7   3.2e-7 / 3.4e-7   3.9e-7 / 3.9e-7   1.0e-6 / 1.1e-6
     dct    1.6e-7 / 1.8e-7   3.8e-7 / 4.2e-7   3.5e-7 / 3.8e-7   1.1e-6 / 1.2e-6   1.8e-7, 3.3e-7
     view   3.1e-7 / 3.5e-7   6.5e-7 / 8.5e-7   6.8e-7 / 7.7e-7   1.8e-6 / 2.7e-6
--p 2, parametrized cases, bars 1 %, one ulp (+ 5e-7), 3.5e-4, 8e-3, 2 %:
+-p 2, parametrized cases (bars: paritylib.FP16_* and the one-ulp bound, in the columns' order):
     arm    differing R          ulps of R     out_l2            out_max           differing output
     exact  0.87 % / 0.87 %      0.99 / 0.99   2.2e-4 / 2.2e-4   2.4e-3 / 2.4e-3   1.98 % / 1.98 %
     odd    0.040 % / 0.051 %    0.99 / 1.0    5.0e-5 / 5.5e-5   2.4e-3 / 2.4e-3   0.084 % / 0.11 %
@@ -52,13 +51,13 @@ import downscale_oracle as S
 import family_sweep_cases as F
 import oddsize_oracle as Q
 import oraclelib as O
+import paritylib as P
 import test_gpu_anysize as A
 import test_gpu_dct as DC
 import test_gpu_downscale as DN
 import test_gpu_exactsize as EX
 import test_gpu_oddsize as OD
 import test_gpu_view as VW
-from test_gpu_oddsize import _m, _rel_l2
 
 pytestmark = pytest.mark.gpu
 
@@ -96,8 +95,7 @@ def _tiny(arm):
 
 
 def _identity(tag, pre, x):
-    _m(tag + " identity", max_err=np.abs(pre - x).max(), l2=_rel_l2(pre, x))
-    assert _rel_l2(pre, x) <= 2e-6 and np.abs(pre - x).max() <= 1e-5
+    P.assert_identity(tag + " identity", pre, x)
 
 
 def _case(arm, k, c, p, u8, pooled=None):
@@ -137,10 +135,7 @@ def _pooled(arm):
     for k, c, u8 in _tiny(arm):
         _case(arm, k, c, 2, u8, pooled=acc)
     if acc:
-        dp, npre, do, nout = (sum(col) for col in zip(*acc))
-        _m("sweep %s pooled p2 (%d cases)" % (arm, len(acc)), pre_diff_frac=dp / npre, out_diff_frac=do / nout, pre_values=npre, out_values=nout)
-        assert dp <= 0.01 * npre
-        assert do <= 0.02 * nout
+        P.pooled_fraction_bars("sweep %s pooled p2 (%d cases)" % (arm, len(acc)), acc)
 
 
 @pytest.mark.parametrize("k,c,p,u8", _params("exact"))

@@ -8,7 +8,8 @@ import numpy as np
 import pytest
 
 import oraclelib as O
-from test_gpu_parity import _rel_l2, _report, _run, _up
+from paritylib import rel_l2, within_one_half_ulp
+from test_gpu_parity import _report, _run, _up
 
 pytestmark = pytest.mark.gpu
 
@@ -42,13 +43,12 @@ def test_specialised_plan_vs_oracle(W, H, precision, flags):
     if precision == 0:
         so = _report(tag + " out", out - oout, 1e-4)
         # (about ten times the measured distributions, profiles/r02_q_pytest_gpu.txt: max 1.2e-6 .. 2.1e-6, p99.99 1.2e-6)
-        assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * 4 <= 1e-5
+        assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * 4 <= 1e-5
         assert so["p99.99"] <= 1.2e-5 and so["max"] <= 2e-5 and so["count_above"] == 0
         d = np.abs(u8.astype(int) - ou8.astype(int))
         assert d.max() <= 1 and (d != 0).mean() <= 5e-4
     else:
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         so = _report(tag + " out", out - oout, 2.0 ** -10)
         assert so["max"] <= 8e-3 and so["p99"] == 0 and so["p99.99"] <= 3e-3 and so["count_above"] <= 5e-4 * so["n"]      # (measured: max <= 4.6e-3, p99.99 <= 1.5e-3, <= 1.5e-4 n)
 
@@ -116,13 +116,12 @@ def test_specialised_integer_factor_vs_oracle(W, H, u, precision, flags):
     tag = "jit %dx%d u%g p%d flags%d" % (W, H, u, precision, flags)
     if precision == 0:
         so = _report(tag + " out", out - oout, 1e-4)
-        assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * u * u <= 1e-5
+        assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * u * u <= 1e-5
         assert so["p99.99"] <= 1.2e-5 and so["max"] <= 2e-5 and so["count_above"] == 0
         d = np.abs(u8.astype(int) - ou8.astype(int))
         assert d.max() <= 1 and (d != 0).mean() <= 5e-4
     else:
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         so = _report(tag + " out", out - oout, 2.0 ** -10)
         assert so["max"] <= 8e-3 and so["p99"] == 0 and so["p99.99"] <= 3e-3 and so["count_above"] <= 5e-4 * so["n"]      # (measured: max <= 4.6e-3, p99.99 <= 1.5e-3, <= 1.5e-4 n)
 

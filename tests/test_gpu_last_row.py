@@ -54,13 +54,14 @@ import numpy as np
 import pytest
 
 import oraclelib as O
-from test_gpu_parity import _knobs_lib, _m, _rel_l2
+from paritylib import measured, rel_l2, within_one_half_ulp
+from test_gpu_parity import _knobs_lib
 
 pytestmark = pytest.mark.gpu
 
 
 @functools.lru_cache(maxsize=None)
-def _frame(kind, W, H, seed):
+def _kind_frame(kind, W, H, seed):
     """(read-only: the cases of one size share their frames)"""
     from vkresample_amd import synth
     f = synth.frame(seed, W, H, kind if kind in "NU" else "N").copy()
@@ -108,8 +109,8 @@ def _rows(tag, got, ref, bar, l2_bar=None):
     above, last, left, right = d[:, :2].max(), d[:, 2].max(), d[:, 2, 0].max(), d[:, 2, -1].max()
     vals = dict(last_row=last, rows_above=above, corner_left=left, corner_right=right, bar=bar)
     if l2_bar is not None:          # (printed where it is asserted: on a black row it is a ratio of two roundings)
-        l2 = vals["last_row_l2"] = _rel_l2(got[:, 2], ref[:, 2])
-    _m(tag, **vals)
+        l2 = vals["last_row_l2"] = rel_l2(got[:, 2], ref[:, 2])
+    measured(tag, **vals)
     assert left <= bar, "%s: pixel (uH-1, 0) off by %g (bar %g; rows uH-3, uH-2: %g)" % (tag, left, bar, above)
     assert right <= bar, ("%s: pixel (uH-1, uW-1), whose E, NE and SE taps all fold onto (uH-1, 0), off by %g (bar %g; rows uH-3, uH-2: %g)"
                           % (tag, right, bar, above))
@@ -195,13 +196,13 @@ class Case:
 def _fft_oracle(W, H, u, precision, kind):
     """(pre-sharpen image, rows uH-3 .. uH-1 of the output and of the 8-bit image) by the full oracle; computed once per frame --
     the cases that differ in their strip cuts share it"""
-    opre, oout, ou8 = O.upscale_rgb8(_frame(kind, W, H, SEED[kind]), u, precision, 0.2)
+    opre, oout, ou8 = O.upscale_rgb8(_kind_frame(kind, W, H, SEED[kind]), u, precision, 0.2)
     return opre, oout[:, -3:].copy(), ou8[-3:].copy()
 
 
 @functools.lru_cache(maxsize=None)
 def _fft_pre_oracle(W, H, u, precision, kind):
-    return O.presharpen_rgb8(_frame(kind, W, H, SEED[kind]), u, precision)
+    return O.presharpen_rgb8(_kind_frame(kind, W, H, SEED[kind]), u, precision)
 
 
 def _fft(W, H, u, precision, reaches, flags=0, ring=1, full=True, **kw):
@@ -218,7 +219,7 @@ def _fft(W, H, u, precision, reaches, flags=0, ring=1, full=True, **kw):
 def _family(W, H, precision, u_e, make, reaches, R_of, **kw):
     """a plan of one of the resampling families: R_of(x) is the family's own oracle for the pre-sharpen image R of input planes x"""
     def oracle(kind):
-        rgb = _frame(kind, W, H, SEED[kind])
+        rgb = _kind_frame(kind, W, H, SEED[kind])
         R = R_of(O.load_lut(precision)[np.transpose(rgb, (2, 0, 1))])
         opre = R.astype(np.float16).astype(np.float64) if precision == 2 else R
         sh = O.sharpen(opre, u_e, precision, 0.2)
@@ -343,7 +344,7 @@ def _run_case(name):
             assert want is not None and abs(_pairs_per_strip(up) - want) < 1e-6 * want, (name, _pairs_per_strip(up), want)
         for kind in case.kinds:
             tag = "last_row %s %s" % (name, kind)
-            rgb = _frame(kind, W, H, SEED[kind])
+            rgb = _kind_frame(kind, W, H, SEED[kind])
             up.upload_rgb8(rgb)
             up.execute(1)
             pre = up.download_presharpen()
@@ -355,16 +356,14 @@ def _run_case(name):
                 assert pre.shape == opre.shape
                 pre = pre.astype(np.float64)
                 if p == 2:
-                    ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-                    assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all(), tag
+                    assert within_one_half_ulp(pre, opre).all(), tag
                     counts.append((int((pre[:, -2:] != opre[:, -2:]).sum()), pre[:, -2:].size, int((out[:, 2] != oout[:, 2]).sum()), out[:, 2].size))
                 _rows(tag + " vs oracle", out, oout, bar, l2_bar)
                 _codes(tag + " u8 vs oracle", u8, ou8, codes)
             elif p == 2 and kind in case.pre_kinds:
                 opre = case.pre_oracle(kind)
                 pre64 = pre.astype(np.float64)
-                ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-                assert (np.abs(pre64 - opre) <= ulp * 1.0001 + 5e-7).all(), tag
+                assert within_one_half_ulp(pre64, opre).all(), tag
                 counts.append((int((pre64[:, -2:] != opre[:, -2:]).sum()), pre64[:, -2:].size, 0, 0))
             # the sharpen alone: rows uH-3 .. uH-1 from rows uH-4 .. uH-1 of the device's own pre-sharpen image
             if not case.own:
@@ -387,7 +386,7 @@ def test_pooled_fp16_fractions():
     acc = [t for name in IDS if _all_cases()[name][0].precision == 2 for t in _run_case(name)]
     assert len(acc) >= 10
     dp, npre, do, nout = (sum(col) for col in zip(*acc))
-    _m("last_row pooled p2 (%d frames)" % len(acc), pre_diff_frac=dp / npre, out_diff_frac=do / nout, pre_values=npre, out_values=nout)
+    measured("last_row pooled p2 (%d frames)" % len(acc), pre_diff_frac=dp / npre, out_diff_frac=do / nout, pre_values=npre, out_values=nout)
     assert dp <= 0.01 * npre
     assert do <= 0.02 * nout
 
@@ -399,7 +398,7 @@ def test_fused_u8_store_last_row(W, H, precision, full):
     code, two at -p 2); at 2048x1024 the reference is the sharpen of the planes plan's own pre-sharpen rows."""
     import vkresample_amd as v
     for kind in ("NUEG" if full else "UG"):
-        rgb = _frame(kind, W, H, SEED[kind])
+        rgb = _kind_frame(kind, W, H, SEED[kind])
         with v.Upscaler(W, H, 2.0, precision) as up:
             _aot(up)
             up.upload_rgb8(rgb)
@@ -426,7 +425,7 @@ def test_output_does_not_depend_on_the_previous_frame(W, H, precision, flags, re
     whole output and its pre-sharpen image are bit for bit those of B on a fresh plan -- with ring = 1 and with three slots, on
     planes and (fused plans) on the fused 8-bit store."""
     import vkresample_amd as v
-    noise, B = _frame("U", W, H, 950), _frame("G", W, H, 951)
+    noise, B = _kind_frame("U", W, H, 950), _kind_frame("G", W, H, 951)
     fused = reaches is not _generic
     for ring in (1, 3):
         for store in ((False, True) if fused else (False,)):
@@ -459,7 +458,7 @@ def test_png_last_scanline():
     from PIL import Image
     import vkresample_amd as v
     W, H = 60, 36
-    rgb = _frame("G", W, H, 960)
+    rgb = _kind_frame("G", W, H, 960)
     with v.Upscaler(W, H, 2.0, 0, 0.2, 0, 0, 1) as up:
         _generic(up)
         out = np.empty((2 * H, 2 * W, 3), np.uint8)

@@ -1,31 +1,22 @@
 """GPU: view plans with FFTUP_FLAG_MIRROR (Upscaler.view(..., flags=FLAG_MIRROR)) -- the view of the frame's half-sample even
 reflection -- against the fp64 cosine-form statement of the rule, tests/mirror_oracle.py, followed by oraclelib.sharpen with the view
-plans' effective factor (quirks B4, B5).
-
-Bars: those of tests/test_gpu_view.py, unchanged.  fp32: the amplitude-preserving image sc * pre, sc = uW uH / (span_x span_y), within
-relative L2 2e-6 and max 1e-5 of the oracle's y; the sharpened output against oraclelib.sharpen applied to the oracle's R within
-relative L2 5e-6 and max 2e-5.  fp16 (-p 2): R within one binary16 ulp of the oracle's own binary16 value and different from it in
-<= 1 % of the pixels; output relative L2 <= 3.5e-4, different in <= 2 %, max 8e-3.  The last output row is compared too (its reads past
-the end of a plane: "same column, last written row", oracle/fftup_oracle.c).
+plans' effective factor (quirks B4, B5), at the bars of tests/paritylib.py, unchanged.  The amplitude-preserving image is
+sc * R, sc = uW uH / (span_x span_y).
 
 Without the mode the library ignores the bit and returns the periodic view: every parity, cross-check, border and name test below
 then fails."""
 import functools
-import os
 import subprocess
 
 import numpy as np
 import pytest
 
 import mirror_oracle as Mo
-import oraclelib as O
+import paritylib as P
 import view_oracle as V
-from test_gpu_dct import _png_read, _png_write
-from test_gpu_oddsize import _frame, _inputs, _m, _rel_l2
+from paritylib import CLI, smooth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 
 
 def _centre(N, M):
@@ -64,57 +55,25 @@ def _oracle_y(x, uW, uH, origin, span):
 
 def _run(W, H, uW, uH, origin, span, precision, flags, rgb=None, planes=None):
     import vkresample_amd as v
-    with v.Upscaler.view(W, H, uW, uH, origin, span, precision, 0.2, 0, flags) as up:
-        if rgb is not None:
-            up.upload_rgb8(rgb)
-        else:
-            up.upload_planar(planes)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
+    with v.Upscaler.view(W, H, uW, uH, origin, span, precision, P.SHARPEN, 0, flags) as up:
+        pre, out = P.run_uploaded(up, rgb, planes)
         names, desc = up.kernel_names, up.description
         assert (up.out_width, up.out_height) == (uW, uH)
         assert not up.tuned and not up.u8_store and up.num_kernels == 4
     return pre, out, names, desc
 
 
-def _smooth(n):
-    for p in (2, 3, 5, 7):
-        while n % p == 0:
-            n //= p
-    return n == 1
-
-
 def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag):
     import vkresample_amd as v
-    rgb, planes, x = _inputs(W, H, precision, uint8, seed)
+    rgb, planes, x = P.inputs(W, H, precision, uint8, seed)
     pre, out, names, desc = _run(W, H, uW, uH, origin, span, precision, _flags(v, extra) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0), rgb, planes)
-    assert names == ["row_r2c_mirror" + ("" if _smooth(W) else "_bz"), "col_view_mirror" + ("" if _smooth(H) else "_bz"), "row_view_c2r_mirror", "sharpen"], names
+    assert names == ["row_r2c_mirror" + ("" if smooth(W) else "_bz"), "col_view_mirror" + ("" if smooth(H) else "_bz"), "row_view_c2r_mirror", "sharpen"], names
     assert "mirror" in desc and "rows %d->%d" % (W, uW) in desc and "columns %d->%d" % (H, uH) in desc, desc
     sc = uW * uH / (span[0] * span[1])
     yv = _oracle_y(x, uW, uH, origin, span)
-    R = yv / sc
     u_e = V.effective_factor(uW, uH, span)
-    assert pre.shape == R.shape == (3, uH, uW)
-    if precision == 0:
-        sh = O.sharpen(R, u_e, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(sc * pre, yv), pre_max=np.abs(sc * pre - yv).max(), out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           last_row_max=np.abs(out[:, -1] - sh[:, -1]).max())
-        assert _rel_l2(sc * pre, yv) <= 2e-6
-        assert np.abs(sc * pre - yv).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5                       # (the last row included)
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u_e, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(), out_l2=_rel_l2(out, sh),
-           out_max=np.abs(out - sh).max(), out_diff_frac=(out != sh).mean(), last_row_max=np.abs(out[:, -1] - sh[:, -1]).max())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        assert (pre != opre).mean() <= 0.01
-        assert (out != sh).mean() <= 0.02
+    assert pre.shape == yv.shape == (3, uH, uW)
+    P.assert_parity(tag, precision, pre, out, yv, sc, u_e)
     return pre, x
 
 
@@ -139,30 +98,30 @@ def test_mirror_plan_against_the_periodic_plan_on_the_extended_frame(W, H, uW, u
     """no oracle: the existing periodic view plan, fed the explicit 2W x 2H even extension built on the host, computes the same
     numbers with the same view and output size.  The pre-sharpen images agree within the sum of the two plans' parity bounds"""
     import vkresample_amd as v
-    _, planes, _ = _inputs(W, H, 0, False, 31)
+    _, planes, _ = P.inputs(W, H, 0, False, 31)
     ext = np.ascontiguousarray(Mo.extend(Mo.extend(planes, 2), 1))
     assert ext.shape == (3, 2 * H, 2 * W) and np.array_equal(ext[:, 2 * H - 1, 2 * W - 1], planes[:, 0, 0])
     a, _, names, _ = _run(W, H, uW, uH, origin, span, 0, _flags(v, extra), planes=planes)
     b, _, pnames, _ = _run(2 * W, 2 * H, uW, uH, origin, span, 0, _flags(v, extra) & ~v.FLAG_MIRROR, planes=ext)
     assert "_mirror" in names[0] and "_mirror" not in pnames[0]
     sc = uW * uH / (span[0] * span[1])
-    _m("mirror vs periodic-on-extension %dx%d->%dx%d" % (W, H, uW, uH), l2=_rel_l2(a, b), max_err=sc * np.abs(a - b).max())
-    assert _rel_l2(a, b) <= 2 * 2e-6 and sc * np.abs(a - b).max() <= 2 * 1e-5
+    P.measured("mirror vs periodic-on-extension %dx%d->%dx%d" % (W, H, uW, uH), l2=P.rel_l2(a, b), max_err=sc * np.abs(a - b).max())
+    assert P.rel_l2(a, b) <= 2 * P.FP32_PRE_L2 and sc * np.abs(a - b).max() <= 2 * P.FP32_PRE_MAX
 
 
 def test_centre_alignment_is_the_dct_mode():
     """40x24 at u = 2, origin = (N/M - 1)/2, span = the frame: the pre-sharpen image of a FFTUP_FLAG_DCT plan on the same frame"""
     import vkresample_amd as v
     W, H, uW, uH = 40, 24, 80, 48
-    _, planes, x = _inputs(W, H, 0, False, 12)
+    _, planes, x = P.inputs(W, H, 0, False, 12)
     a, _, _, _ = _run(W, H, uW, uH, (_centre(W, uW), _centre(H, uH)), (float(W), float(H)), 0, v.FLAG_MIRROR, planes=planes)
     with v.Upscaler(W, H, 2.0, 0, 0.2, 0, v.FLAG_DCT) as up:
         up.upload_planar(planes)
         up.execute(1)
         b = up.download_presharpen().astype(np.float64)
     sc = 4.0
-    _m("mirror centre-aligned vs dct 40x24 u2", l2=_rel_l2(a, b), max_err=sc * np.abs(a - b).max())
-    assert _rel_l2(a, b) <= 2e-6 and sc * np.abs(a - b).max() <= 1e-5
+    P.measured("mirror centre-aligned vs dct 40x24 u2", l2=P.rel_l2(a, b), max_err=sc * np.abs(a - b).max())
+    assert P.rel_l2(a, b) <= P.FP32_PRE_L2 and sc * np.abs(a - b).max() <= P.FP32_PRE_MAX
 
 
 def test_border_of_a_ramp():
@@ -174,7 +133,7 @@ def test_border_of_a_ramp():
     origin, span, sc = (_centre(W, uW), _centre(H, uH)), (float(W), float(H)), 4.0
     mir, _, _, _ = _run(W, H, uW, uH, origin, span, 0, v.FLAG_MIRROR, planes=planes)
     per, _, _, _ = _run(W, H, uW, uH, origin, span, 0, 0, planes=planes)
-    _m("ramp 32->64", mirror_min=(sc * mir).min(), mirror_max=(sc * mir).max(), periodic_min=(sc * per).min(), periodic_max=(sc * per).max())
+    P.measured("ramp 32->64", mirror_min=(sc * mir).min(), mirror_max=(sc * mir).max(), periodic_min=(sc * per).min(), periodic_max=(sc * per).max())
     assert (sc * mir).min() >= -0.01 and (sc * mir).max() <= 1.01
     assert (sc * per).min() < -0.1 and (sc * per).max() > 1.1
 
@@ -182,7 +141,7 @@ def test_border_of_a_ramp():
 def test_set_view_gives_the_bytes_of_a_fresh_plan():
     import vkresample_amd as v
     W, H, uW, uH = 48, 40, 40, 36
-    rgb = _frame(W, H, seed=9)
+    rgb = P.frame(W, H, seed=9)
     # a pan at the same span (only one table changes), a zoom out past the frame (fewer spectrum columns), back in (more)
     seq = [((10.3, 7.75), (17.9, 12.2)), ((11.05, 7.5), (17.9, 12.2)), ((-2.0, 1.0), (150.0, 50.0)), ((3.0, 4.0), (8.0, 6.0))]
     fresh = []
@@ -216,9 +175,9 @@ def test_execute_device_and_ring(precision):
     """one mirror view through fftup_execute_device (both formats), the ring and the host-streamed queue: the bytes of
     upload -> execute -> download"""
     import vkresample_amd as v
-    from test_gpu_device_io import PLANAR, RGB8, _device_run
+    from devimage import PLANAR, RGB8, device_run
     W, H, uW, uH, origin, span = REFLECTED[:6]
-    frames = [np.ascontiguousarray(_frame(W, H, seed=40 + k)) for k in range(3)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=40 + k)) for k in range(3)]
     with v.Upscaler.view(W, H, uW, uH, origin, span, precision, flags=v.FLAG_MIRROR, ring=3) as up:
         want8, wantp = [], []
         for f in frames:
@@ -226,9 +185,9 @@ def test_execute_device_and_ring(precision):
             up.execute(1)
             want8.append(up.download_rgb8())
             wantp.append(up.download_planar().tobytes())
-        got, clean = _device_run(up, RGB8, frames[1], RGB8)
+        got, clean = device_run(up, RGB8, frames[1], RGB8)
         assert clean and got.tobytes() == want8[1].tobytes()
-        got, clean = _device_run(up, RGB8, frames[2], PLANAR, out_padded=True)
+        got, clean = device_run(up, RGB8, frames[2], PLANAR, out_padded=True)
         assert clean and got.tobytes() == wantp[2]
         for s, f in enumerate(frames):
             up.upload_rgb8(f, s)
@@ -244,7 +203,7 @@ def test_mirror_cli(tmp_path):
     """-size 40x36 -view 10.3,7.75,17.9,12.2 -mirror on a 48x40 PNG gives the API's pixels; -mirror without a view exits 1 with a
     message and writes nothing"""
     import vkresample_amd as v
-    rgb = _frame(48, 40, seed=78)
+    rgb = P.frame(48, 40, seed=78)
     got = []
     for flags in (v.FLAG_MIRROR, 0):
         with v.Upscaler.view(48, 40, 40, 36, (10.3, 7.75), (17.9, 12.2), flags=flags) as up:
@@ -253,14 +212,14 @@ def test_mirror_cli(tmp_path):
             got.append(up.download_rgb8())
     want, periodic = got
     assert not np.array_equal(want, periodic)
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
 
     def cli(*args):
         return subprocess.run([CLI] + list(args), capture_output=True, text=True, cwd=tmp_path, timeout=120)
 
     r = cli("-i", "in.png", "-o", "out.png", "-size", "40x36", "-view", "10.3,7.75,17.9,12.2", "-mirror", "-n", "1")
     assert r.returncode == 0, r.stdout + r.stderr
-    assert np.array_equal(_png_read(tmp_path / "out.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "out.png"), want)
     for bad in (["-u", "2", "-mirror"], ["-size", "40x36", "-mirror"], ["-size", "40x36", "-centres", "-mirror"]):
         r = cli("-i", "in.png", "-o", "bad.png", *bad)
         assert r.returncode == 1 and "-mirror needs" in r.stdout and not (tmp_path / "bad.png").exists(), bad
@@ -270,7 +229,7 @@ def test_mirror_cli(tmp_path):
 def test_existing_plans_give_the_same_bytes_beside_a_mirror_plan():
     """a periodic view plan and a -u 2 plan before, while and after a mirror plan exists in the process"""
     import vkresample_amd as v
-    rgb, rgb2 = _frame(240, 126, seed=7), _frame(50, 32, seed=8)
+    rgb, rgb2 = P.frame(240, 126, seed=7), P.frame(50, 32, seed=8)
 
     def both():
         got = []

@@ -24,6 +24,7 @@ import numpy as np
 import pytest
 
 import oraclelib as O
+from paritylib import measured, one_half_ulp_bound, rel_l2, within_one_half_ulp
 
 pytestmark = pytest.mark.gpu
 
@@ -31,16 +32,6 @@ pytestmark = pytest.mark.gpu
 def _up(*a, **k):
     import vkresample_amd as v
     return v.Upscaler(*a, **k)
-
-
-def _rel_l2(a, b):
-    return float(np.linalg.norm((a - b).ravel()) / max(np.linalg.norm(b.ravel()), 1e-30))
-
-
-def _m(tag, **vals):
-    """measured error figures of a comparison, printed (pytest -s -> profiles/*_parity_small.txt): the asserted bounds sit at
-    about ten times the largest figure any parametrisation printed"""
-    print("MEASURED %s: %s" % (tag, "  ".join("%s %.3g" % kv for kv in vals.items())))
 
 
 def _run(W, H, u, precision, dist, flags=0, sharpen=0.2, seed=0):
@@ -68,20 +59,20 @@ SIZES_FP32 = [
 def test_fp32_parity_small(W, H, u, dist):
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, 0, dist)
     usq = u * u
-    _m("fp32_small %dx%d u%g %s" % (W, H, u, dist), pre_l2=_rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq,
-       out_l2=_rel_l2(out, oout), out_max=np.abs(out - oout).max())
-    assert _rel_l2(pre, opre) <= 2e-6
+    measured("fp32_small %dx%d u%g %s" % (W, H, u, dist), pre_l2=rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq,
+             out_l2=rel_l2(out, oout), out_max=np.abs(out - oout).max())
+    assert rel_l2(pre, opre) <= 2e-6
     assert np.abs(pre - opre).max() * usq <= 1e-5
     # (uniform noise: the filter's sqrt at exact zeros, see the module docstring; -u 1 keeps every exact 0 and 1)
     l2_max, out_max = (5e-6, 2e-5) if dist == "N" else ((3e-4, 2.5e-3) if u == 1.0 else (5e-6, 5e-4))
-    assert _rel_l2(out, oout) <= l2_max
+    assert rel_l2(out, oout) <= l2_max
     assert np.abs(out - oout).max() <= out_max
     # sharpen kernel in isolation: same (device) input on both sides (two-launch path, where the
     # pre-sharpen planes are exactly what the sharpen kernel read)
     from vkresample_amd import FLAG_UNFUSED_SHARPEN
     (pre_u, out_u, _), _ = _run(W, H, u, 0, dist, flags=FLAG_UNFUSED_SHARPEN)
     sh = O.sharpen(pre_u, u, 0, 0.2)
-    _m("fp32_small sharpen alone %dx%d u%g %s" % (W, H, u, dist), max=np.abs(out_u - sh).max())
+    measured("fp32_small sharpen alone %dx%d u%g %s" % (W, H, u, dist), max=np.abs(out_u - sh).max())
     # uniform noise: n = 1 - mx cancels in fp32 for near-saturated neighbourhoods (as in the reference's fp32 shader)
     assert np.abs(out_u - sh).max() <= (3e-6 if dist == "N" else 1e-4)
     # u8 = trunc(255*x): a float error can flip the truncation by one code; for u == 1 every exact
@@ -104,14 +95,12 @@ def test_fp32_fused_u8_load_identical(W, H, u):
 @pytest.mark.parametrize("dist", ["U", "N"])
 def test_fp16_parity_small(W, H, u, dist):
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, 2, dist)
-    # pre-sharpen: both sides are fp16 values; fp32-vs-fp64 FFT noise can flip a rounding -> <= 1 ulp
-    ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-    # (+5e-7: below |g| ~ 2^-14 the fp16 grid (2^-24) is finer than the fp32 transform's own noise)
-    assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-    _m("fp16_small %dx%d u%g %s" % (W, H, u, dist), pre_diff_frac=(pre != opre).mean(), out_l2=_rel_l2(out, oout),
-       out_max=np.abs(out - oout).max(), out_diff_frac=(out != oout).mean())
+    # pre-sharpen: both sides are fp16 values; fp32-vs-fp64 FFT noise can flip a rounding -> <= 1 ulp (paritylib)
+    assert within_one_half_ulp(pre, opre).all()
+    measured("fp16_small %dx%d u%g %s" % (W, H, u, dist), pre_diff_frac=(pre != opre).mean(), out_l2=rel_l2(out, oout),
+             out_max=np.abs(out - oout).max(), out_diff_frac=(out != oout).mean())
     assert (pre != opre).mean() <= 0.01      # ringing around zero: fp16 ulp shrinks with |g|, fp32 noise does not
-    assert _rel_l2(out, oout) <= 3.5e-4 and (out != oout).mean() <= 0.02
+    assert rel_l2(out, oout) <= 3.5e-4 and (out != oout).mean() <= 0.02
     assert np.abs(out - oout).max() <= 8e-3
     # the half-arithmetic sharpen is bit-exact given the same fp16 input (two-launch path)
     from vkresample_amd import FLAG_UNFUSED_SHARPEN
@@ -126,7 +115,7 @@ def test_tuned_equals_generic(precision):
     from vkresample_amd import FLAG_GENERIC_KERNELS
     (pre, out, u8), _ = _run(512, 256, 2.0, precision, "N")
     (pre2, out2, u82), _ = _run(512, 256, 2.0, precision, "N", flags=FLAG_GENERIC_KERNELS)
-    _m("tuned_vs_generic p%d" % precision, pre_max=np.abs(pre - pre2).max() * 4, out_max=np.abs(out - out2).max(), out_diff_frac=(out != out2).mean())
+    measured("tuned_vs_generic p%d" % precision, pre_max=np.abs(pre - pre2).max() * 4, out_max=np.abs(out - out2).max(), out_diff_frac=(out != out2).mean())
     assert np.abs(pre - pre2).max() * 4 <= (4e-6 if precision == 0 else 1e-3)           # (measured 4.2e-7 / one binary16 ulp)
     assert np.abs(out - out2).max() <= (2e-5 if precision == 0 else 4e-3)              # (1.6e-6 / 2.4e-3 = five ulps)
     assert precision == 0 or (out != out2).mean() <= 2.5e-3                              # (2.2e-4)
@@ -278,9 +267,9 @@ def _check_full_size(W, H, precision, flags, dist, tagx=""):
     if precision == 0:
         sp = _report(tag + " pre*u^2", (pre - opre) * 4, 1e-5)
         so = _report(tag + " out", out - oout, 1e-4)
-        assert _rel_l2(pre, opre) <= 2e-6
+        assert rel_l2(pre, opre) <= 2e-6
         assert sp["max"] <= 1e-5 and sp["p99.99"] <= 5e-6 and sp["count_above"] == 0
-        assert _rel_l2(out, oout) <= 1e-5
+        assert rel_l2(out, oout) <= 1e-5
         if dist == "N":
             assert so["max"] <= 2e-5 and so["p99.99"] <= 1.2e-5 and so["count_above"] == 0
         else:
@@ -288,12 +277,11 @@ def _check_full_size(W, H, precision, flags, dist, tagx=""):
         d = np.abs(u8.astype(int) - ou8.astype(int))
         assert d.max() <= 1 and (d != 0).mean() <= 5e-4
     else:
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         # in binary16 ulps of the output (ulp at 0.5..1 = 4.9e-4): the sharpen amplifies one-ulp input flips
         # (measured: p99 0, p99.99 one ulp = 9.8e-4, max 2e-3 .. 3.4e-3, 4e-6 .. 8e-5 of the pixels above one ulp)
         so = _report(tag + " out", out - oout, 2.0 ** -10)
-        assert _rel_l2(out, oout) <= 3e-4
+        assert rel_l2(out, oout) <= 3e-4
         assert so["max"] <= 6e-3 and so["p99"] == 0 and so["p99.99"] <= 2e-3 and so["count_above"] <= 4e-4 * so["n"]
 
 
@@ -310,7 +298,7 @@ def test_config1_literal_image_api(flags):
     (pre, out, u8), (opre, oout, ou8) = _run_rgb(d["rgb"], 2.0, 0, flags=flags)
     assert np.abs(oout[:, 1000:1064, 1800:1864] - d["out_crop"]).max() <= 1e-12       # the oracle build is sane
     so = _report("config1 no_upscaling.png flags%d out" % flags, out - oout, 1e-4)
-    assert np.abs(pre - opre).max() * 4 <= 1e-5 and _rel_l2(pre, opre) <= 2e-6
+    assert np.abs(pre - opre).max() * 4 <= 1e-5 and rel_l2(pre, opre) <= 2e-6
     assert so["p99.99"] <= 1.5e-5 and so["max"] <= 1e-4 and so["count_above"] == 0        # (measured 1.4e-6 / 9e-6)
     dd = np.abs(u8.astype(int) - ou8.astype(int))
     print("PARITY config1 u8: differing codes %.2e, max %d" % ((dd != 0).mean(), dd.max()))
@@ -353,7 +341,7 @@ def test_fused_sharpen_equals_unfused(precision, pps, monkeypatch):
     if precision == 0:
         # different row pairing -> different fp32 rounding of the same numbers
         assert np.abs(out - out2).max() <= 1e-4
-        assert _rel_l2(out, out2) <= 2e-6
+        assert rel_l2(out, out2) <= 2e-6
         # the quirk column x = uW-1 and the strip-boundary rows are where the bookkeeping lives
         assert np.abs(out[:, :, -1] - out2[:, :, -1]).max() <= 1e-4
     else:
@@ -374,15 +362,14 @@ def test_golden_vectors_gpu(name):
         assert np.abs(pre - d["pre"]).max() <= 1e-12 and np.abs(out - d["out"]).max() <= 1e-9
         assert np.abs(u8.astype(int) - d["u8"].astype(int)).max() <= 1
     elif precision == 0:
-        _m("golden " + name, pre_max=np.abs(pre - d["pre"]).max() * 4, pre_l2=_rel_l2(pre, d["pre"]),
-           out_max=np.abs(out - d["out"]).max(), out_l2=_rel_l2(out, d["out"]))
-        assert np.abs(pre - d["pre"]).max() * 4 <= 4e-6 and _rel_l2(pre, d["pre"]) <= 2e-6                     # (measured 3.9e-7, 1.6e-7)
-        assert np.abs(out - d["out"]).max() <= 1e-5 and _rel_l2(out, d["out"]) <= 3e-6     # (7.9e-7, 3.0e-7)
+        measured("golden " + name, pre_max=np.abs(pre - d["pre"]).max() * 4, pre_l2=rel_l2(pre, d["pre"]),
+                 out_max=np.abs(out - d["out"]).max(), out_l2=rel_l2(out, d["out"]))
+        assert np.abs(pre - d["pre"]).max() * 4 <= 4e-6 and rel_l2(pre, d["pre"]) <= 2e-6                     # (measured 3.9e-7, 1.6e-7)
+        assert np.abs(out - d["out"]).max() <= 1e-5 and rel_l2(out, d["out"]) <= 3e-6     # (7.9e-7, 3.0e-7)
         assert np.abs(u8.astype(int) - d["u8"].astype(int)).max() <= 1
     else:
-        ulp = np.maximum(np.abs(d["pre"]), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - d["pre"]) <= ulp * 1.0001 + 5e-7).all()
-        _m("golden " + name, out_max=np.abs(out - d["out"]).max(), out_diff_frac=(out != d["out"]).mean())
+        assert within_one_half_ulp(pre, d["pre"]).all()
+        measured("golden " + name, out_max=np.abs(out - d["out"]).max(), out_diff_frac=(out != d["out"]).mean())
         assert np.abs(out - d["out"]).max() <= 4e-3 and (out != d["out"]).mean() <= 2e-3      # (7.3e-4, 1.7e-4)
 
 
@@ -446,10 +433,10 @@ def test_u8_wrap_flag():
 def test_largest_r2c_size_vs_oracle():
     """uW = 8192 is the largest width the reference's R2C path accepts (VkResample.cpp:1424)."""
     (pre, out, u8), (opre, oout, ou8) = _run(4096, 64, 2.0, 0, "N", seed=9)
-    _m("largest_r2c", pre_l2=_rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * 4, out_l2=_rel_l2(out, oout),
-       out_max=np.abs(out - oout).max())
-    assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * 4 <= 6e-6                  # (measured 1.6e-7, 5.4e-7)
-    assert _rel_l2(out, oout) <= 4e-6 and np.abs(out - oout).max() <= 2e-5     # (4.0e-7, 1.7e-6)
+    measured("largest_r2c", pre_l2=rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * 4, out_l2=rel_l2(out, oout),
+             out_max=np.abs(out - oout).max())
+    assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * 4 <= 6e-6                  # (measured 1.6e-7, 5.4e-7)
+    assert rel_l2(out, oout) <= 4e-6 and np.abs(out - oout).max() <= 2e-5     # (4.0e-7, 1.7e-6)
 
 
 @pytest.mark.parametrize("W,H,u,precision,flags", [(4608, 64, 2.0, 0, 0), (4608, 64, 2.0, 0, 2), (3072, 32, 3.0, 0, 0),
@@ -466,15 +453,14 @@ def test_non_r2c_complex_path_vs_oracle(W, H, u, precision, flags):
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, precision, "N", flags=flags, seed=21)
     usq = u * u
     if precision == 0:
-        _m("non_r2c %dx%d u%g" % (W, H, u), pre_l2=_rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=_rel_l2(out, oout))
-        assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6               # (measured <= 1.8e-7, 5.2e-7)
+        measured("non_r2c %dx%d u%g" % (W, H, u), pre_l2=rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=rel_l2(out, oout))
+        assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6               # (measured <= 1.8e-7, 5.2e-7)
         so = _report("non-R2C %dx%d u%g out" % (W, H, u), out - oout, 1e-4)
-        assert _rel_l2(out, oout) <= 5e-6 and so["max"] <= 1.5e-5 and so["p99.99"] <= 1e-5     # (4.3e-7, 1.4e-6, 1.1e-6)
+        assert rel_l2(out, oout) <= 5e-6 and so["max"] <= 1.5e-5 and so["p99.99"] <= 1e-5     # (4.3e-7, 1.4e-6, 1.1e-6)
     elif precision == 2:
         # -p 2 beyond the R2C limit (VERDICT r2 missing 1): half input and half complex pre-sharpen image around fp32
         # transforms (VR:1420-1424, VF:7282-7292), the complex sharpen in binary16 arithmetic (VR:865-907 with f16vec2)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         so = _report("non-R2C -p 2 %dx%d u%g out" % (W, H, u), out - oout, 2.0 ** -10)
         assert so["max"] <= 8e-3 and so["p99"] == 0 and so["p99.99"] <= 3e-3
         d = np.abs(u8.astype(int) - ou8.astype(int))
@@ -526,13 +512,12 @@ def test_four_step_rows_vs_oracle(W, H, u, precision, flags):
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, precision, "N", flags=flags, seed=23)
     usq = u * u
     if precision == 0:
-        _m("four_step %dx%d u%g" % (W, H, u), pre_l2=_rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=_rel_l2(out, oout),
-           out_max=np.abs(out - oout).max())
-        assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6
-        assert _rel_l2(out, oout) <= 5e-6 and np.abs(out - oout).max() <= 2e-5      # (measured <= 1.9e-7, 4.8e-7; 4.3e-7, 1.4e-6)
+        measured("four_step %dx%d u%g" % (W, H, u), pre_l2=rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=rel_l2(out, oout),
+                 out_max=np.abs(out - oout).max())
+        assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6
+        assert rel_l2(out, oout) <= 5e-6 and np.abs(out - oout).max() <= 2e-5      # (measured <= 1.9e-7, 4.8e-7; 4.3e-7, 1.4e-6)
     elif precision == 2:
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         so = _report("four-step -p 2 %dx%d u%g out" % (W, H, u), out - oout, 2.0 ** -10)
         assert so["max"] <= 8e-3 and so["p99"] == 0 and so["p99.99"] <= 3e-3
     else:
@@ -558,13 +543,12 @@ def test_four_step_columns_vs_oracle(W, H, u, precision, flags):
     (pre, out, u8), (opre, oout, ou8) = _run(W, H, u, precision, "N", flags=flags, seed=29)
     usq = u * u
     if precision == 0:
-        _m("tall %dx%d u%g" % (W, H, u), pre_l2=_rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=_rel_l2(out, oout),
-           out_max=np.abs(out - oout).max())
-        assert _rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6
-        assert _rel_l2(out, oout) <= 5e-6 and np.abs(out - oout).max() <= 2e-5
+        measured("tall %dx%d u%g" % (W, H, u), pre_l2=rel_l2(pre, opre), pre_max=np.abs(pre - opre).max() * usq, out_l2=rel_l2(out, oout),
+                 out_max=np.abs(out - oout).max())
+        assert rel_l2(pre, opre) <= 2e-6 and np.abs(pre - opre).max() * usq <= 6e-6
+        assert rel_l2(out, oout) <= 5e-6 and np.abs(out - oout).max() <= 2e-5
     elif precision == 2:
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
+        assert within_one_half_ulp(pre, opre).all()
         so = _report("tall -p 2 %dx%d u%g out" % (W, H, u), out - oout, 2.0 ** -10)
         assert so["max"] <= 8e-3 and so["p99"] == 0 and so["p99.99"] <= 3e-3
     else:
@@ -1049,7 +1033,7 @@ def test_generic_polyphase_column_pass(W, H, precision, flags, monkeypatch):
             res.append((up.download_presharpen().astype(np.float64), up.download_planar().astype(np.float64)))
     opre, oout, _ = O.upscale_rgb8(rgb, 2.0, precision, 0.2)
     # (-p 2: the pre-sharpen image is binary16 -- one ulp of the value, as the sweeps' bound)
-    tol_pre = {0: 2e-6, 1: 1e-12}.get(precision, np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10 * 1.0001 + 5e-7)
+    tol_pre = {0: 2e-6, 1: 1e-12}.get(precision, one_half_ulp_bound(opre))
     for pre, out in res:
         assert (np.abs(pre - opre) <= tol_pre).all()
     assert (np.abs(res[0][0] - res[1][0]) <= tol_pre).all()

@@ -2,15 +2,9 @@
 computed as chirp-z transforms -- against the fp64 dense-matrix statement of the rule, tests/view_oracle.py, followed by
 oraclelib.sharpen with the effective factor u_e = (float)sqrt(uW uH / (span_x span_y)) (quirks B4, B5).
 
-Bars: the project's Bluestein and odd-size bars, as stated in tests/test_gpu_oddsize.py -- the construction is the same (a cyclic
-convolution through two Stockham transforms of a smooth length, tables from the host).  fp32: the amplitude-preserving image
-sc * pre, sc = uW uH / (span_x span_y), within relative L2 2e-6 and max 1e-5 of the oracle's y; the sharpened output against
-oraclelib.sharpen applied to the oracle's R within relative L2 5e-6 and max 2e-5.  fp16 (-p 2): R within one binary16 ulp of the
-oracle's own binary16 value and different from it in <= 1 % of the pixels; output relative L2 <= 3.5e-4, different in <= 2 %, max
-8e-3.  The last output row is compared too: its reads
-past the end of a plane, undefined in the reference (quirk B5), are defined here as "same column, last written row"
-(oracle/fftup_oracle.c), and the HIP path is held to that definition."""
-import os
+Bars: those of tests/paritylib.py, the bars of the Bluestein and odd-size plans -- the construction is the same (a cyclic
+convolution through two Stockham transforms of a smooth length, tables from the host).  The amplitude-preserving image is
+sc * R, sc = uW uH / (span_x span_y)."""
 import subprocess
 
 import numpy as np
@@ -18,14 +12,11 @@ import pytest
 
 import exactsize_oracle as E
 import family_sweep_cases as F
-import oraclelib as O
+import paritylib as P
 import view_oracle as V
-from test_gpu_dct import _png_read, _png_write
-from test_gpu_oddsize import _frame, _inputs, _m, _rel_l2
+from paritylib import CLI
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 
 # full-frame lattices: fold and split, an odd output row, kept Nyquist bins, a tail row, Bluestein forward transforms
 FULL = [(50, 32, 32, 50, ""), (40, 30, 25, 48, ""), (64, 48, 64, 72, ""), (45, 21, 64, 21, ""), (46, 22, 70, 30, "any")]
@@ -41,14 +32,8 @@ def _flags(v, extra):
 
 def _run(W, H, uW, uH, origin, span, precision, flags, rgb=None, planes=None):
     import vkresample_amd as v
-    with v.Upscaler.view(W, H, uW, uH, origin, span, precision, 0.2, 0, flags) as up:
-        if rgb is not None:
-            up.upload_rgb8(rgb)
-        else:
-            up.upload_planar(planes)
-        up.execute(1)
-        pre = up.download_presharpen().astype(np.float64)
-        out = up.download_planar().astype(np.float64)
+    with v.Upscaler.view(W, H, uW, uH, origin, span, precision, P.SHARPEN, 0, flags) as up:
+        pre, out = P.run_uploaded(up, rgb, planes)
         names, desc = up.kernel_names, up.description
         assert (up.out_width, up.out_height) == (uW, uH)
         assert not up.tuned and not up.u8_store and up.num_kernels == 4
@@ -60,7 +45,7 @@ def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag, y=Non
     compared with the dense statement as well -- or, with dense=False (lengths of thousands), in its place; `pooled`: a list that
     takes the -p 2 counts (differing, all) of R and of the output in place of the two fraction bars"""
     import vkresample_amd as v
-    rgb, planes, x = _inputs(W, H, precision, uint8, seed)
+    rgb, planes, x = P.inputs(W, H, precision, uint8, seed)
     pre, out, names, desc = _run(W, H, uW, uH, origin, span, precision, _flags(v, extra) | (v.FLAG_FUSE_U8_LOAD if uint8 else 0), rgb, planes)
     assert names[0] in ("row_r2c_odd", "row_r2c_odd_bz") and names[1] in ("col_view", "col_view_bz") and names[2:] == ["row_view_c2r", "sharpen"], names
     # (a Bluestein forward transform per axis whose input length is not smooth: FLAG_ANY_SIZE allows it, the lengths decide)
@@ -69,34 +54,11 @@ def _check(W, H, uW, uH, origin, span, precision, extra, uint8, seed, tag, y=Non
     assert "rows %d->%d" % (W, uW) in desc and "columns %d->%d" % (H, uH) in desc and "origin" in desc and "span" in desc, desc
     sc = uW * uH / (span[0] * span[1])
     yv = V.view_planes(x, uW, uH, origin, span) if dense else y(x)
-    R = yv / sc
     u_e = V.effective_factor(uW, uH, span)
-    assert pre.shape == R.shape == (3, uH, uW)
+    assert pre.shape == yv.shape == (3, uH, uW)
     if y is not None and dense:
         assert np.abs(y(x) - yv).max() <= 1e-12                         # (the two oracles agree on this lattice)
-    if precision == 0:
-        sh = O.sharpen(R, u_e, 0, 0.2)
-        _m(tag, pre_l2=_rel_l2(sc * pre, yv), pre_max=np.abs(sc * pre - yv).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max())
-        assert _rel_l2(sc * pre, yv) <= 2e-6
-        assert np.abs(sc * pre - yv).max() <= 1e-5
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u_e, 2, 0.2)
-        _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max(),
-           out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(),
-           out_diff_frac=(out != sh).mean())
-        assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        if pooled is None:
-            assert (pre != opre).mean() <= 0.01
-            assert (out != sh).mean() <= 0.02
-        else:                                   # (an output of a few dozen values: the two fractions are asserted on the pooled counts)
-            pooled.append((int((pre != opre).sum()), pre.size, int((out != sh).sum()), out.size))
+    P.assert_parity(tag, precision, pre, out, yv, sc, u_e, pooled=pooled)
     return pre, x
 
 
@@ -135,20 +97,20 @@ def test_cosine_comes_back_at_the_view_positions(W, H, uW, uH, origin, span, ext
         pre, _, _, _ = _run(W, H, uW, uH, origin, span, 0, _flags(v, extra), planes=x)
         want = np.broadcast_to(0.5 + a * np.cos(2 * np.pi * k * pos / W + 0.4), (3, uH, uW))
         # (the rows are cosines of the fp32 input, not of `row`: the interpolant of the rounding differences is within 2^-24 * a few)
-        _m("view cosine %d->%d k=%d" % (W, uW, k), max_err=np.abs(sc * pre - want).max(), l2=_rel_l2(sc * pre, want))
-        assert _rel_l2(sc * pre, want) <= 2e-6
-        assert np.abs(sc * pre - want).max() <= 1e-5
+        P.measured("view cosine %d->%d k=%d" % (W, uW, k), max_err=np.abs(sc * pre - want).max(), l2=P.rel_l2(sc * pre, want))
+        assert P.rel_l2(sc * pre, want) <= P.FP32_PRE_L2
+        assert np.abs(sc * pre - want).max() <= P.FP32_PRE_MAX
 
 
 @pytest.mark.parametrize("W,H,uW,uH,origin,span,extra", VIEWS[:2])
 def test_rolling_the_input_is_moving_the_origin(W, H, uW, uH, origin, span, extra):
     import vkresample_amd as v
-    _, planes, _ = _inputs(W, H, 0, False, 21)
+    _, planes, _ = P.inputs(W, H, 0, False, 21)
     sc = uW * uH / (span[0] * span[1])
     a, _, _, _ = _run(W, H, uW, uH, (origin[0] + 3, origin[1] + 3), span, 0, _flags(v, extra), planes=planes)
     b, _, _, _ = _run(W, H, uW, uH, origin, span, 0, _flags(v, extra), planes=np.ascontiguousarray(np.roll(planes, (-3, -3), axis=(1, 2))))
-    _m("view roll %dx%d->%dx%d" % (W, H, uW, uH), max_err=sc * np.abs(a - b).max(), l2=_rel_l2(a, b))
-    assert _rel_l2(a, b) <= 2e-6 and sc * np.abs(a - b).max() <= 1e-5
+    P.measured("view roll %dx%d->%dx%d" % (W, H, uW, uH), max_err=sc * np.abs(a - b).max(), l2=P.rel_l2(a, b))
+    assert P.rel_l2(a, b) <= P.FP32_PRE_L2 and sc * np.abs(a - b).max() <= P.FP32_PRE_MAX
 
 
 def test_largest_row_convolution():
@@ -164,7 +126,7 @@ def test_largest_row_convolution():
 def test_set_view_gives_the_bytes_of_a_fresh_plan():
     import vkresample_amd as v
     W, H, uW, uH = 48, 40, 40, 36
-    rgb = _frame(W, H, seed=9)
+    rgb = P.frame(W, H, seed=9)
     # a pan at the same span (only one table changes), a zoom out past the frame (fewer spectrum columns), back in (more)
     seq = [((10.3, 7.75), (17.9, 12.2)), ((11.05, 7.5), (17.9, 12.2)), ((-2.0, 1.0), (96.0, 50.0)), ((3.0, 4.0), (8.0, 6.0))]
     fresh = []
@@ -205,9 +167,9 @@ def test_set_view_gives_the_bytes_of_a_fresh_plan():
 def test_execute_device_ring_and_download_rgb8(precision):
     """one view through fftup_execute_device (both formats), the ring and the host-streamed queue: the bytes of upload -> execute -> download"""
     import vkresample_amd as v
-    from test_gpu_device_io import PLANAR, RGB8, _device_run
+    from devimage import PLANAR, RGB8, device_run
     W, H, uW, uH, origin, span = 45, 21, 64, 30, (-3.25, 2.5), (61.5, 33.3)
-    frames = [np.ascontiguousarray(_frame(W, H, seed=40 + k)) for k in range(3)]
+    frames = [np.ascontiguousarray(P.frame(W, H, seed=40 + k)) for k in range(3)]
     with v.Upscaler.view(W, H, uW, uH, origin, span, precision, ring=3) as up:
         want8, wantp = [], []
         for f in frames:
@@ -215,9 +177,9 @@ def test_execute_device_ring_and_download_rgb8(precision):
             up.execute(1)
             want8.append(up.download_rgb8())
             wantp.append(up.download_planar().tobytes())
-        got, clean = _device_run(up, RGB8, frames[1], RGB8)
+        got, clean = device_run(up, RGB8, frames[1], RGB8)
         assert clean and got.tobytes() == want8[1].tobytes()
-        got, clean = _device_run(up, RGB8, frames[2], PLANAR, out_padded=True)
+        got, clean = device_run(up, RGB8, frames[2], PLANAR, out_padded=True)
         assert clean and got.tobytes() == wantp[2]
         for s, f in enumerate(frames):
             up.upload_rgb8(f, s)
@@ -235,12 +197,12 @@ def test_view_cli(tmp_path):
     """-size 40x36 -view 10.3,7.75,17.9,12.2 on a 48x40 PNG gives the API's pixels; -view without -size, with -centres or malformed
     exits 1 with a message and writes nothing"""
     import vkresample_amd as v
-    rgb = _frame(48, 40, seed=78)
+    rgb = P.frame(48, 40, seed=78)
     with v.Upscaler.view(48, 40, 40, 36, (10.3, 7.75), (17.9, 12.2)) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
         want = up.download_rgb8()
-    _png_write(tmp_path / "in.png", rgb)
+    P.png_write(tmp_path / "in.png", rgb)
 
     def cli(*args):
         return subprocess.run([CLI] + list(args), capture_output=True, text=True, cwd=tmp_path, timeout=120)
@@ -248,7 +210,7 @@ def test_view_cli(tmp_path):
     r = cli("-i", "in.png", "-o", "out.png", "-size", "40x36", "-view", "10.3,7.75,17.9,12.2", "-n", "1")
     assert r.returncode == 0, r.stdout + r.stderr
     assert "48x40 to 40x36" in r.stdout and "view" in r.stdout
-    assert np.array_equal(_png_read(tmp_path / "out.png"), want)
+    assert np.array_equal(P.png_read(tmp_path / "out.png"), want)
     for bad in (["-view", "10.3,7.75,17.9,12.2", "-u", "2"], ["-size", "40x36", "-centres", "-view", "10.3,7.75,17.9,12.2"],
                 ["-size", "40x36", "-view", "10.3,7.75,17.9"], ["-size", "40x36", "-view", "0,0,9000,12"]):
         r = cli("-i", "in.png", "-o", "bad.png", *bad)
@@ -258,7 +220,7 @@ def test_view_cli(tmp_path):
 def test_existing_plans_give_the_same_bytes_beside_a_view_plan():
     """a plan of fftup_plan_create and one of fftup_plan_create_size before, while and after a view plan exists in the process"""
     import vkresample_amd as v
-    rgb, rgb2 = _frame(240, 126, seed=7), _frame(50, 32, seed=8)
+    rgb, rgb2 = P.frame(240, 126, seed=7), P.frame(50, 32, seed=8)
 
     def both():
         got = []

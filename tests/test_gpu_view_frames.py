@@ -1,29 +1,24 @@
 """GPU: fftup_execute_device_views -- a view per frame on a view plan, the chirp tables of each frame built on the device by
 k_view_tables ahead of the frame's kernels -- against the oracles of the view plans (tests/view_oracle.py, tests/mirror_oracle.py)
-at the bars of tests/test_gpu_view.py and tests/test_gpu_mirror.py, unchanged: fp32 pre-sharpen relative L2 2e-6 and max 1e-5,
-output 5e-6 and 2e-5; -p 2 pre-sharpen within one binary16 ulp and different in <= 1 %, output relative L2 3.5e-4, max 8e-3,
-different in <= 2 %.  The last output row is included.  And against a fresh plan created with the frame's view (host tables): the two
-table sets differ by single fp32 rounding steps in a few entries, so the fp32 planes agree to relative L2 2e-7 -- about one
-rounding step; for -p 2 the fraction of differing values is reported."""
+at the bars of tests/paritylib.py, unchanged (only the call's last frame has a pre-sharpen image: the others are held to the output
+bars alone).  And against a fresh plan created with the frame's view (host tables): the two table sets differ by single fp32
+rounding steps in a few entries, so the fp32 planes agree to relative L2 2e-7 -- about one rounding step; for -p 2 the fraction of
+differing values is reported."""
 import ctypes as C
-import os
 import re
 import subprocess
 
 import numpy as np
 import pytest
 
-import oraclelib as O
+import paritylib as P
 import view_oracle as V
-from test_gpu_dct import _png_read, _png_write
-from test_gpu_device_io import ESZ, FILL, PLANAR, RGB8, _Image
+from devimage import ESZ, FILL, PLANAR, RGB8, Image
+from paritylib import CLI
 from test_gpu_mirror import _oracle_y as _mirror_y
-from test_gpu_oddsize import _frame, _inputs, _m, _rel_l2
 from test_host_mirror import _longdouble_tables as _mirror_tables
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CLI = os.path.join(ROOT, "vkresample_amd", "vkresample")
 
 W, H, UW, UH = 48, 40, 40, 36
 # frame i runs on lane i % 3 (FFTUP_STREAMS, default 3): the four views of test_set_view_gives_the_bytes_of_a_fresh_plan (a pan, a
@@ -38,8 +33,8 @@ def _views_run(up, frames, fmt_in, views, fmt_out=PLANAR):
     """frames[i] (rgb or planes, by fmt_in) through ONE execute_device_views call -> (per frame the output in dense order, the
     pre-sharpen image of the call's last frame); the bytes around every image must stay untouched"""
     esz = ESZ[up.precision]
-    src = [_Image(fmt_in, up.width, up.height, esz, False, frame=f) for f in frames]
-    dst = [_Image(fmt_out, up.out_width, up.out_height, esz) for _ in frames]
+    src = [Image(fmt_in, up.width, up.height, esz, False, frame=f) for f in frames]
+    dst = [Image(fmt_out, up.out_width, up.out_height, esz) for _ in frames]
     try:
         up.execute_device_views([s.image for s in src], [d.image for d in dst], views)
         outs = []
@@ -51,33 +46,6 @@ def _views_run(up, frames, fmt_in, views, fmt_out=PLANAR):
     finally:
         for im in src + dst:
             im.close()
-
-
-def _against_oracle(tag, precision, pre, out, yv, sc, u_e):
-    """the bars of tests/test_gpu_view.py::_check / tests/test_gpu_mirror.py::_check (pre None: the output alone)"""
-    R = yv / sc
-    out = out.astype(np.float64)
-    if precision == 0:
-        sh = O.sharpen(R, u_e, 0, 0.2)
-        _m(tag, out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(), last_row_max=np.abs(out[:, -1] - sh[:, -1]).max())
-        assert _rel_l2(out, sh) <= 5e-6
-        assert np.abs(out - sh).max() <= 2e-5
-        if pre is not None:
-            _m(tag, pre_l2=_rel_l2(sc * pre, yv), pre_max=np.abs(sc * pre - yv).max())
-            assert _rel_l2(sc * pre, yv) <= 2e-6
-            assert np.abs(sc * pre - yv).max() <= 1e-5
-    else:
-        opre = R.astype(np.float16).astype(np.float64)
-        ulp = np.maximum(np.abs(opre), 2.0 ** -14) * 2.0 ** -10
-        sh = O.sharpen(opre, u_e, 2, 0.2)
-        _m(tag, out_l2=_rel_l2(out, sh), out_max=np.abs(out - sh).max(), out_diff_frac=(out != sh).mean(), last_row_max=np.abs(out[:, -1] - sh[:, -1]).max())
-        assert _rel_l2(out, sh) <= 3.5e-4
-        assert np.abs(out - sh).max() <= 8e-3
-        assert (out != sh).mean() <= 0.02
-        if pre is not None:
-            _m(tag, pre_diff_frac=(pre != opre).mean(), pre_max_ulps=(np.abs(pre - opre) / ulp).max())
-            assert (np.abs(pre - opre) <= ulp * 1.0001 + 5e-7).all()
-            assert (pre != opre).mean() <= 0.01
 
 
 def _fresh(shape, view, precision, flags, frame, fmt_in):
@@ -94,17 +62,17 @@ def _fresh(shape, view, precision, flags, frame, fmt_in):
 
 def _against_fresh(tag, precision, out, fresh):
     if precision == 0:
-        _m(tag, fresh_l2=_rel_l2(out.astype(np.float64), fresh.astype(np.float64)), fresh_diff_frac=(out != fresh).mean())
-        assert _rel_l2(out.astype(np.float64), fresh.astype(np.float64)) <= 2e-7
+        P.measured(tag, fresh_l2=P.rel_l2(out.astype(np.float64), fresh.astype(np.float64)), fresh_diff_frac=(out != fresh).mean())
+        assert P.rel_l2(out.astype(np.float64), fresh.astype(np.float64)) <= 2e-7
     else:
-        _m(tag, fresh_diff_frac=(out != fresh).mean())
+        P.measured(tag, fresh_diff_frac=(out != fresh).mean())
 
 
 def _moving(precision, fmt_in):
     import vkresample_amd as v
     uploads, xs = [], []
     for k in range(len(MOVING)):
-        rgb, planes, x = _inputs(W, H, precision, fmt_in == RGB8, 60 + k)
+        rgb, planes, x = P.inputs(W, H, precision, fmt_in == RGB8, 60 + k)
         uploads.append(rgb if fmt_in == RGB8 else planes)
         xs.append(x)
     ys = [V.view_planes(x, UW, UH, o, s) for x, (o, s) in zip(xs, MOVING)]
@@ -115,7 +83,7 @@ def _moving(precision, fmt_in):
             outs, pre = _views_run(up, uploads[:n], fmt_in, MOVING[:n])
             for k in (range(n) if n == len(MOVING) else [n - 1]):
                 (o, s) = MOVING[k]
-                _against_oracle("views p%d in%d frame %d of %d" % (precision, fmt_in, k, n), precision, pre if k == n - 1 else None, outs[k], ys[k],
+                P.assert_parity("views p%d in%d frame %d of %d" % (precision, fmt_in, k, n), precision, pre if k == n - 1 else None, outs[k], ys[k],
                                 UW * UH / (s[0] * s[1]), V.effective_factor(UW, UH, s))
     for k, view in enumerate(MOVING):
         _against_fresh("views p%d in%d frame %d" % (precision, fmt_in, k), precision, outs[k], _fresh((W, H, UW, UH), view, precision, 0, uploads[k], fmt_in))
@@ -146,7 +114,7 @@ def test_mirror_views(precision):
     flags = v.FLAG_MIRROR | v.FLAG_ANY_SIZE
     uploads, xs = [], []
     for k in range(len(views)):
-        _, planes, x = _inputs(w, h, precision, False, 80 + k)
+        _, planes, x = P.inputs(w, h, precision, False, 80 + k)
         uploads.append(planes)
         xs.append(x)
     with v.Upscaler.view(w, h, uw, uh, (0.0, 0.0), (float(w), float(h)), precision, 0.2, 0, flags) as up:
@@ -155,7 +123,7 @@ def test_mirror_views(precision):
             outs, pre = _views_run(up, uploads[:n], PLANAR, views[:n])
             for k in (range(n) if n == len(views) else [n - 1]):
                 (o, s) = views[k]
-                _against_oracle("mirror views p%d frame %d of %d" % (precision, k, n), precision, pre if k == n - 1 else None, outs[k],
+                P.assert_parity("mirror views p%d frame %d of %d" % (precision, k, n), precision, pre if k == n - 1 else None, outs[k],
                                 _mirror_y(xs[k], uw, uh, o, s), uw * uh / (s[0] * s[1]), V.effective_factor(uw, uh, s))
     for k, view in enumerate(views):
         _against_fresh("mirror views p%d frame %d" % (precision, k), precision, outs[k], _fresh((w, h, uw, uh), view, precision, flags, uploads[k], PLANAR))
@@ -169,12 +137,12 @@ def test_longest_convolution():
     views = [((0.5, 0.0), (4096.0, 8.0)), ((1000.25, 0.0), (2048.0, 8.0))]
     ins = []
     for k in range(2):
-        _, planes, x = _inputs(w, h, 0, False, 5 + k)
+        _, planes, x = P.inputs(w, h, 0, False, 5 + k)
         ins.append((planes, x))
     with v.Upscaler.view(w, h, w, h, (0.0, 0.0), (float(w), float(h))) as up:
         assert "L=8192" in up.description
         outs, pre = _views_run(up, [ins[0][0]], PLANAR, views[:1])
-        _against_oracle("views 4096x8 half-pixel shift L=8192", 0, pre, outs[0], V.shift_planes(ins[0][1], (0.5, 0.0)), 1.0, V.effective_factor(w, h, views[0][1]))
+        P.assert_parity("views 4096x8 half-pixel shift L=8192", 0, pre, outs[0], V.shift_planes(ins[0][1], (0.5, 0.0)), 1.0, V.effective_factor(w, h, views[0][1]))
         first = outs[0].tobytes()
         outs, _ = _views_run(up, [i[0] for i in ins], PLANAR, views)
         assert outs[0].tobytes() == first
@@ -193,7 +161,7 @@ def _table_bars(tag, got, want):
         a = a.astype(np.complex128)
         worst = max(np.abs(a.real - b.real).max(), np.abs(a.imag - b.imag).max())
         top = max(np.abs(b.real).max(), np.abs(b.imag).max())
-        _m("%s %s" % (tag, name), max_diff=worst, max_table=top, steps=worst / top * 2.0 ** 23)
+        P.measured("%s %s" % (tag, name), max_diff=worst, max_table=top, steps=worst / top * 2.0 ** 23)
         assert worst <= 2.0 ** -23 * top
 
 
@@ -203,7 +171,7 @@ def test_tables_against_longdouble_numpy(monkeypatch):
     last: a zoom, and a pan that rebuilt only `pre` beside chirp tables two frames old) and a mirror plan on one lane"""
     import vkresample_amd as v
     monkeypatch.setenv("FFTUP_STREAMS", "3")
-    frames = [_inputs(W, H, 0, False, 30 + k)[1] for k in range(5)]
+    frames = [P.inputs(W, H, 0, False, 30 + k)[1] for k in range(5)]
     with v.Upscaler.view(W, H, UW, UH, (0.0, 0.0), (float(W), float(H))) as up:
         with pytest.raises(v.FftupError) as e:
             up.download_view_tables(0, 0)
@@ -219,7 +187,7 @@ def test_tables_against_longdouble_numpy(monkeypatch):
     w, h, uw, uh = 46, 22, 70, 30
     view = ((-3.25, 0.6), (61.5, 11.0))
     with v.Upscaler.view(w, h, uw, uh, (0.0, 0.0), (float(w), float(h)), 0, 0.2, 0, v.FLAG_MIRROR | v.FLAG_ANY_SIZE) as up:
-        _views_run(up, [_inputs(w, h, 0, False, 36)[1]], PLANAR, [view])
+        _views_run(up, [P.inputs(w, h, 0, False, 36)[1]], PLANAR, [view])
         _table_bars("tables mirror x", up.download_view_tables(0, 0), _mirror_tables(w, uw, view[0][0], view[1][0]))
         _table_bars("tables mirror y", up.download_view_tables(0, 1), _mirror_tables(h, uh, view[0][1], view[1][1]))
     with v.Upscaler(64, 48, 2.0) as up:
@@ -230,9 +198,9 @@ def test_tables_against_longdouble_numpy(monkeypatch):
 
 def test_the_plan_keeps_its_view():
     import vkresample_amd as v
-    rgb = _frame(W, H, seed=9)
+    rgb = P.frame(W, H, seed=9)
     own = ((10.3, 7.75), (17.9, 12.2))
-    frames = [_inputs(W, H, 0, False, 50 + k)[1] for k in range(4)]
+    frames = [P.inputs(W, H, 0, False, 50 + k)[1] for k in range(4)]
     with v.Upscaler.view(W, H, UW, UH, own[0], own[1]) as up:
         up.upload_rgb8(rgb)
         up.execute(1)
@@ -240,7 +208,7 @@ def test_the_plan_keeps_its_view():
         outs, pre = _views_run(up, frames, PLANAR, MOVING[2:6])
         # the tap is the call's last frame: its sharpened image is that frame's output
         s = MOVING[5][1]
-        _against_oracle("tap after views", 0, pre, outs[3], V.view_planes(frames[3].astype(np.float64), UW, UH, MOVING[5][0], s), UW * UH / (s[0] * s[1]),
+        P.assert_parity("tap after views", 0, pre, outs[3], V.view_planes(frames[3].astype(np.float64), UW, UH, MOVING[5][0], s), UW * UH / (s[0] * s[1]),
                         V.effective_factor(UW, UH, s))
         buf = C.create_string_buffer(512)
         assert up._lib.fftup_plan_describe(up._h, buf, 512) == 0 and buf.value.decode() == before[1]
@@ -264,9 +232,9 @@ def test_refusals_leave_the_outputs_untouched():
     nan = float("nan")
 
     def refused(up, views, *words):
-        frames = [_inputs(up.width, up.height, 0, False, 70 + k)[1] for k in range(len(views))]
-        src = [_Image(PLANAR, up.width, up.height, 4, False, frame=f) for f in frames]
-        dst = [_Image(PLANAR, up.out_width, up.out_height, 4) for _ in frames]
+        frames = [P.inputs(up.width, up.height, 0, False, 70 + k)[1] for k in range(len(views))]
+        src = [Image(PLANAR, up.width, up.height, 4, False, frame=f) for f in frames]
+        dst = [Image(PLANAR, up.out_width, up.out_height, 4) for _ in frames]
         try:
             with pytest.raises(v.FftupError) as e:
                 up.execute_device_views([s.image for s in src], [d.image for d in dst], views)
@@ -285,8 +253,8 @@ def test_refusals_leave_the_outputs_untouched():
         refused(up, [MOVING[0], MOVING[1], ((nan, 0.0), (17.9, 12.2)), MOVING[3]], "finite", "views[2]")
         refused(up, [MOVING[0], ((0.0, 0.0), (9.0 * UW, 12.2))], "span_x", "views[1]")
         refused(up, [((0.0, 0.0), (17.9, 9.0 * UH))], "span_y", "views[0]")
-        src = _Image(PLANAR, W, H, 4, False, frame=_inputs(W, H, 0, False, 70)[1])
-        dst = _Image(PLANAR, UW, UH, 4)
+        src = Image(PLANAR, W, H, 4, False, frame=P.inputs(W, H, 0, False, 70)[1])
+        dst = Image(PLANAR, UW, UH, 4)
         try:
             a, b = (v._lib.DeviceImageDesc * 1)(src.image.desc()), (v._lib.DeviceImageDesc * 1)(dst.image.desc())
             assert up._lib.fftup_execute_device_views(up._h, a, b, None, 1, None) == 1 and b"views is null" in up._lib.fftup_last_error()
@@ -300,8 +268,8 @@ def test_view_clip_cli(tmp_path):
     """-viewto ... -frames 4: four files, each the bytes of execute_device_views fed the doubles of the printed `view k:` lines; the
     bad invocations exit non-zero and write nothing"""
     import vkresample_amd as v
-    rgb = _frame(W, H, seed=78)
-    _png_write(tmp_path / "in.png", rgb)
+    rgb = P.frame(W, H, seed=78)
+    P.png_write(tmp_path / "in.png", rgb)
 
     def cli(*args):
         return subprocess.run([CLI] + list(args), capture_output=True, text=True, cwd=tmp_path, timeout=120)
@@ -316,7 +284,7 @@ def test_view_clip_cli(tmp_path):
     with v.Upscaler.view(W, H, UW, UH, *views[0]) as up:
         outs, _ = _views_run(up, [rgb] * 4, RGB8, views, RGB8)
     for k in range(4):
-        assert np.array_equal(_png_read(tmp_path / ("clip_%04d.png" % (k + 1))), outs[k].reshape(UH, UW, 3)), k
+        assert np.array_equal(P.png_read(tmp_path / ("clip_%04d.png" % (k + 1))), outs[k].reshape(UH, UW, 3)), k
     for bad in (["-size", "40x36", "-viewto", "3,4,8,6", "-frames", "4"], ["-size", "40x36", "-view", "10.3,7.75,17.9,12.2", "-viewto", "3,4,8,6"],
                 ["-size", "40x36", "-view", "10.3,7.75,17.9,12.2", "-viewto", "3,4,8", "-frames", "4"],
                 ["-size", "40x36", "-view", "10.3,7.75,17.9,12.2", "-viewto", "3,4,8,6", "-frames", "1"]):

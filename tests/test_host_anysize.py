@@ -8,6 +8,8 @@ import re
 import numpy as np
 import pytest
 
+from paritylib import rel_l2, smooth
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (W, H, u, extra flags): sizes with a prime factor above 7 somewhere among W, H, uW, uH
@@ -76,16 +78,9 @@ def test_smooth_plans_stay_valid_with_the_flag():
 
 
 # ---------------------------------------------------------------- the kernel's arithmetic in numpy
-def _smooth(n):
-    for p in (2, 3, 5, 7):
-        while n % p == 0:
-            n //= p
-    return n == 1
-
-
 def _bluestein_length(N):
     L = 2 * N - 1
-    while not _smooth(L):
+    while not smooth(L):
         L += 1
     return L
 
@@ -120,10 +115,6 @@ def _bluestein32(x, integer_phase=True):
     return (c[:N] * w32).astype(np.complex64)
 
 
-def _rel_l2(a, b):
-    return float(np.linalg.norm(a - b) / np.linalg.norm(b))
-
-
 @pytest.mark.parametrize("N", [46, 1366, 2732, 4094])
 def test_bluestein_fp32_model_accuracy(N):
     """A Bluestein transform in fp32 with integer-reduced chirp tables is a few times a direct fp32 transform's error (measured
@@ -134,13 +125,13 @@ def test_bluestein_fp32_model_accuracy(N):
     rng = np.random.default_rng(N)
     x = (rng.random(N) + 1j * rng.random(N)).astype(np.complex64)
     ref = np.fft.fft(x.astype(np.complex128))
-    err = _rel_l2(_bluestein32(x).astype(np.complex128), ref)
+    err = rel_l2(_bluestein32(x).astype(np.complex128), ref)
     M = N + 2
-    while not _smooth(M):
+    while not smooth(M):
         M += 2
     xs = (rng.random(M) + 1j * rng.random(M)).astype(np.complex64)
-    direct = _rel_l2(_fft32(xs).astype(np.complex128), np.fft.fft(xs.astype(np.complex128)))
-    bad = _rel_l2(_bluestein32(x, integer_phase=False).astype(np.complex128), ref)
+    direct = rel_l2(_fft32(xs).astype(np.complex128), np.fft.fft(xs.astype(np.complex128)))
+    bad = rel_l2(_bluestein32(x, integer_phase=False).astype(np.complex128), ref)
     print("MEASURED bluestein model N=%d L=%d: rel L2 %.3g, direct fp32 at %d: %.3g (ratio %.1f), fp32 phase: %.3g"
           % (N, _bluestein_length(N), err, M, direct, err / direct, bad))
     assert err < 5e-7                      # four transforms per pixel: < 2e-6, the fp32 parity bar of tests/test_gpu_downscale.py

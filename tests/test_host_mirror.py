@@ -11,21 +11,15 @@ import pytest
 
 import mirror_oracle as Mo
 import plan_driver
+from family_sweep_cases import smooth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MIRROR, ANY, DCT = 4096, 1024, 256
 
 
-def _smooth(n):
-    for p in (2, 3, 5, 7):
-        while n % p == 0:
-            n //= p
-    return n == 1
-
-
 def _conv(N, M):
     L = 2 * N + M
-    while not _smooth(L):
+    while not smooth(L):
         L += 1
     return L
 
@@ -78,7 +72,7 @@ def test_accepted_sizes_and_their_geometry(planner):
         assert Lx <= 8192 and Lx >= 2 * W + uW and Ly >= 2 * H + uH
         # the forward transforms keep the input's lengths; the buffers those of the worst case
         assert g["planW"].startswith("%d:" % W) and g["planH"].startswith("%d:" % H) and g["ncols"] == str(W // 2 + 1)
-        assert g["bzL"] == per["bzL"] and (g["bz"] == "1") == (not (_smooth(W) and _smooth(H)))
+        assert g["bzL"] == per["bzL"] and (g["bz"] == "1") == (not (smooth(W) and smooth(H)))
         tk = int(g["TK"])
         assert tk in (1, 2, 4, 8) and int(g["ldsCol"]) <= lds_max and int(g["ldsRowI"]) <= lds_max
         assert int(g["ldsRowI"]) >= 16 * Lx and int(g["ldsCol"]) >= 16 * Ly * tk

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import view_oracle as V
+from family_sweep_cases import smooth
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -149,7 +150,7 @@ def test_host_tables_against_longdouble_numpy(tables_driver, N, M, origin, span)
     k, opre, opost, oc = V.chirp_tables(N, M, origin, span)
     assert kmax == k == V.kmax(N, M, span)
     need = 2 * (N // 2) + M
-    assert L >= need and _smooth(L) and not any(_smooth(q) for q in range(need, L))      # the smallest smooth length that fits
+    assert L >= need and smooth(L) and not any(smooth(q) for q in range(need, L))      # the smallest smooth length that fits
     eps = 2.0 ** -24
     assert np.abs(pre - opre.astype(np.complex128)).max() <= 1.01 * eps
     scale = float(span) / M / N
@@ -159,10 +160,3 @@ def test_host_tables_against_longdouble_numpy(tables_driver, N, M, origin, span)
     cw[d % L] = oc.astype(np.complex128)
     ref = np.fft.ifft(cw)                                               # FFT with exp(+...) / L
     assert np.abs(bhat - ref).max() <= 1.01 * eps * max(np.abs(ref).max(), 1e-30) + 1e-12
-
-
-def _smooth(n):
-    for p in (2, 3, 5, 7):
-        while n % p == 0:
-            n //= p
-    return n == 1
