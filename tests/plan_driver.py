@@ -15,13 +15,14 @@ def golden_rows(name):
         return json.load(f)
 
 
-def build(d):
-    """the driver's executable in the directory `d`"""
-    exe = os.path.join(str(d), "plan_rules_driver")
+def build(d, name="plan_rules_driver", knobs=False):
+    """the executable of the driver tests/`name`.cpp in the directory `d`, linked with the library's objects; knobs: with the
+    objects of libfftup_knobs.so (jit_knobs.o in place of jit.o: FFTUP_EXPERIMENT is read)"""
+    exe = os.path.join(str(d), name + ("_knobs" if knobs else ""))
     obj = os.path.join(ROOT, "build", "obj")
-    objs = sorted(os.path.join(obj, f) for f in os.listdir(obj) if f.endswith(".o") and f != "jit_knobs.o")
+    objs = sorted(os.path.join(obj, f) for f in os.listdir(obj) if f.endswith(".o") and f != ("jit.o" if knobs else "jit_knobs.o"))
     subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-std=c++17", "-O1", "-I", os.path.join(ROOT, "vkresample_amd", "csrc"),
-                           "-x", "hip", os.path.join(ROOT, "tests", "plan_rules_driver.cpp"), "-x", "none"] + objs + ["-o", exe])
+                           "-x", "hip", os.path.join(ROOT, "tests", name + ".cpp"), "-x", "none"] + objs + ["-o", exe])
     return exe
 
 

@@ -1,4 +1,4 @@
-"""Builds the built-in wisdom table of csrc/jit.hpp: runs the plan-time tuner (FFTUP_FLAG_TUNE_PLAN) over common widths
+"""Builds the built-in wisdom table of csrc/jit_choose.cpp: runs the plan-time tuner (FFTUP_FLAG_TUNE_PLAN) over common widths
 and upscale factors on this device and prints the decisions that differ from the chooser's pick.
   python tools/gpu_wisdom.py > gpurun_out/<tag>/wisdom_builtin.txt"""
 import os

@@ -11,6 +11,7 @@
 //   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views and the device / stream helpers
 //   fftup_align.hip    shift estimates: the aligner object (fftup_align_*), beside the plan, and the launches of kernels_align.hpp
 //   jit.cpp            the plan-time compiler
+//   jit_choose.cpp     the plan-time chooser: which factorizations a specialised plan runs (no device)
 #pragma once
 #include <hip/hip_runtime.h>
 

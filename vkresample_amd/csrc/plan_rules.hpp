@@ -11,7 +11,7 @@
 
 #include "../../include/fftup.h"
 #include "fft_engine.hpp"
-#include "jit.hpp"
+#include "jit_choose.hpp"
 
 using fftup::StagePlan;
 
