@@ -291,6 +291,19 @@ ORC_API int orc_sharpen(const orc_config* c, const double* R, double* out, uint3
     return 0;
 }
 
+/* the same filter on a complex image (the non-R2C path below): len = |u^2 z| */
+ORC_API int orc_sharpen_complex(const orc_config* c, const double* re, const double* im, double* out, uint32_t uW, uint32_t uH)
+{
+    const int half = c->precision == 2;
+    double upsq = const_via_percent_f((double)(c->upscale * c->upscale), c->precision);
+    double coef = const_via_percent_f((double)c->sharpen, c->precision);
+    for (int ch = 0; ch < 3; ch++) {
+        const uint64_t o = (uint64_t)ch * uW * uH;
+        sharpen_plane(re + o, im + o, out + o, uW, uH, upsq, coef, half);
+    }
+    return 0;
+}
+
 /* ------------------------------------------------------------------ the non-R2C path
  * VR:1424: performR2C = bufferStride[0] <= maxComputeSharedMemorySize / complexSizeCalc, i.e. uW <= 8192 (4096 for
  * -p 1) with the 64 KB the reference's planner assumes; wider outputs take a full complex 2-D transform:

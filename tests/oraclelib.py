@@ -143,6 +143,17 @@ def sharpen(R, upscale=2.0, precision=0, sharpen=0.2):
     return out
 
 
+def sharpen_complex(z, upscale=2.0, precision=0, sharpen=0.2):
+    """the filter of the non-R2C path on a complex image z [3][uH][uW]: its taps are |u^2 z|"""
+    re, im = np.ascontiguousarray(z.real, dtype=np.float64), np.ascontiguousarray(z.imag, dtype=np.float64)
+    _, uH, uW = re.shape
+    cfg = _cfg(0, 0, upscale, precision, sharpen)
+    out = np.empty_like(re)
+    lib().orc_sharpen_complex(C.byref(cfg), re.ctypes.data_as(C.c_void_p), im.ctypes.data_as(C.c_void_p), out.ctypes.data_as(C.c_void_p),
+                              C.c_uint32(uW), C.c_uint32(uH))
+    return out
+
+
 _MAX_THREADS = None
 
 

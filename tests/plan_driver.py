@@ -26,10 +26,10 @@ def build(d, name="plan_rules_driver", knobs=False):
     return exe
 
 
-def request_line(entry, width, height, upscale=1.0, precision=0, flags=0, ring=0, out=(0, 0), align=0, view=(0.0, 0.0, 0.0, 0.0)):
-    """one request in the driver's input format (floats in hex)"""
+def request_line(entry, width, height, upscale=1.0, precision=0, flags=0, ring=0, out=(0, 0), align=0, view=(0.0, 0.0, 0.0, 0.0), sharpen=None):
+    """one request in the driver's input format (floats in hex); sharpen None: the driver's 0.2"""
     return " ".join([entry, str(width), str(height), float(upscale).hex(), str(precision), str(flags), str(ring),
-                     str(out[0]), str(out[1]), str(align)] + [float(x).hex() for x in view])
+                     str(out[0]), str(out[1]), str(align)] + [float(x).hex() for x in view] + ([] if sharpen is None else [float(sharpen).hex()]))
 
 
 def run(exe, d, requests):

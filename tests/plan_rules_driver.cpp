@@ -1,6 +1,6 @@
 // plan_rules_driver.cpp -- the device-free planner (csrc/plan_rules.hpp) without a device: reads "device LDS_BYTES COMPUTE_UNITS ARCH"
 // and one request per line (entry width height upscale precision flags ring out_width out_height align origin_x origin_y span_x
-// span_y; floats in hex) from standard input, runs plan_check + plan_geometry on each and prints every PlanGeometry field
+// span_y [sharpen]; floats in hex) from standard input, runs plan_check + plan_geometry on each and prints every PlanGeometry field
 // (plan_geometry_print.hpp), or "error CODE TEXT".  A fftup_jit::choose that succeeds stands for a specialisation that loaded.
 // Linked with the library's object files (tests/test_host_plan_rules.py).
 #include <cstdio>
@@ -39,6 +39,7 @@ int main()
         in >> cfg.width >> cfg.height >> f[0] >> cfg.precision >> cfg.flags >> cfg.ring >> size[0] >> size[1] >> align >> f[1] >> f[2] >> f[3] >> f[4];
         if (!in) { fprintf(stderr, "bad request line: %s\n", line.c_str()); return 2; }
         cfg.channels = 3; cfg.sharpen = 0.2f; cfg.upscale = strtof(f[0].c_str(), nullptr);
+        if (std::string s; in >> s) cfg.sharpen = strtof(s.c_str(), nullptr);          // (optional last field: the strength, 0.2 without it)
         const fftup_view view = {strtod(f[1].c_str(), nullptr), strtod(f[2].c_str(), nullptr), strtod(f[3].c_str(), nullptr), strtod(f[4].c_str(), nullptr)};
         PlanRequest rq;
         rq.cfg = &cfg;
