@@ -545,7 +545,9 @@ FFTUP_API int fftup_stream_destroy(void* stream);
  *   1. luma = 0.2126 R + 0.7152 G + 0.0722 B (RGB8: code / 255; PLANAR: the stored value), box mean over d x d, crop, times the
  *      separable window w[n] = 1/2 - 1/2 cos(2 pi (n + 1/2) / N): a (ref) and b (cur).
  *   2. ONE complex transform Z = DFT2(a + i b); A[k] = (Z[k] + conj Z[-k]) / 2, B[k] = (Z[k] - conj Z[-k]) / 2i.
- *   3. P = B conj(A), R = P / |P|; R = 0 outside the band and where |P| <= 1e-9 |P[0,0]|.
+ *   3. P = B conj(A), R = P / |P|; R = 0 outside the band and where |P| <= 1e-9 |P[0,0]|.  P[0,0] = 0 -- a frame that is black in
+ *      the window: R = 0 everywhere (what step 2 leaves in the black frame's transform is rounding, not signal), and steps 4-6
+ *      give dx = dy = -d, peak = peak_coarse = 0 by the tie rule alone.
  *   4. r = Re IDFT2(R); coarse peak p = argmax over the n_x x n_y grid (lowest row-major index on a tie),
  *      peak_coarse = r_max n_x n_y / K (identical frames: 1).
  *   5. r(u, v) = (1 / n_x n_y) Re sum_k R[k] exp(2 pi i (k_x u / n_x + k_y v / n_y)) on the (2 kappa + 1)^2 points

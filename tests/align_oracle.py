@@ -53,8 +53,10 @@ def _signed(n):
 
 
 def estimate(ref, cur, g, single=False):
-    """steps 1-6 for one pair -> dict(dx, dy, peak, peak_coarse, coarse=(p_x, p_y), fine=(i, j), gap, near): gap is the difference
-    between the best and the second-best coarse value, in peak_coarse units; near: the coarse values within 1e-3 of the best, itself included.  single: complex64 / float32 arithmetic from step 2 on"""
+    """steps 1-6 for one pair -> dict(dx, dy, peak, peak_coarse, coarse=(p_x, p_y), fine=(i, j), dx_, dy_, K, gap, near): gap is the
+    difference between the best and the second-best coarse value, in peak_coarse units; near: the coarse values within 1e-3 of the best,
+    itself included; dx_, dy_: the parabola's vertex per axis, in fine cells from the fine maximum, in [-0.5, 0.5]; K: the bins of the
+    band.  single: complex64 / float32 arithmetic from step 2 on"""
     ct, ft = (np.complex64, np.float32) if single else (np.complex128, np.float64)
     nx, ny, d, kappa = g["nx"], g["ny"], g["d"], g["kappa"]
     a, b = windowed(ref, g).astype(ft), windowed(cur, g).astype(ft)
@@ -68,7 +70,7 @@ def estimate(ref, cur, g, single=False):
     sx, sy = _signed(nx), _signed(ny)
     band = (np.abs(sy)[:, None] <= g["band_ky"]) & (np.abs(sx)[None, :] <= g["band_kx"])
     K = int(band.sum())
-    keep = band & (mag > ft(1e-9) * mag[0, 0])
+    keep = band & (mag > ft(1e-9) * mag[0, 0]) & (mag[0, 0] > 0)          # (P[0,0] = 0, a black frame: no bin carries signal)
     R = np.zeros_like(P)
     R[keep] = P[keep] / mag[keep]
     # 4. coarse peak
@@ -100,7 +102,7 @@ def estimate(ref, cur, g, single=False):
     s_x -= nx * np.floor((s_x + nx / 2) / nx)
     s_y -= ny * np.floor((s_y + ny / 2) / ny)
     return dict(dx=float(d * s_x), dy=float(d * s_y), peak=float(F[j, i] * scale), peak_coarse=float(flat[p] * scale),
-                coarse=(px, py), fine=(i, j), gap=float((flat[order[0]] - flat[order[1]]) * scale),
+                coarse=(px, py), fine=(i, j), dx_=float(dx_), dy_=float(dy_), K=K, gap=float((flat[order[0]] - flat[order[1]]) * scale),
                 near=[float(flat[q] * scale) for q in order[:8] if (flat[order[0]] - flat[q]) * scale <= 1e-3])
 
 

@@ -138,7 +138,12 @@ static __global__ void k_align_cols(AlignParams p)
         if (tid < h) { red[tid].x += red[tid + h].x; red[tid].y += red[tid + h].y; }
         __syncthreads();
     }
-    const float floor_p = 1e-9f * fabsf(red[0].x * red[0].y);
+    // P[0,0] = 0: a frame that is black in the window.  Its transform is zero in exact arithmetic, but A and B come out of ONE packed
+    // transform, and the separation leaves a rounding residue of the other frame in it -- unit phasors of noise that a floor of 0
+    // would let through (a peak of 0.14 at 64 x 32).  Such a pair has no signal: R = 0 everywhere.
+    const float p00 = fabsf(red[0].x * red[0].y);
+    const bool live = p00 > 0.0f;
+    const float floor_p = 1e-9f * p00;
     float2* f = fft_lds<-1, 2>(a, b, p.planY, p.twY, tid, T);
     float2* o = f == a ? b : a;
     const int sx0 = c0 < nx - c0 ? c0 : c0 - nx;      // signed k_x of the two columns, in [-n_x/2, n_x/2)
@@ -153,7 +158,7 @@ static __global__ void k_align_cols(AlignParams p)
         const int sy = ky < ny - ky ? ky : ky - ny;
         const bool band = (sy < 0 ? -sy : sy) <= p.bky;
         float2 Rv = make_float2(0.0f, 0.0f);
-        if (band && mag > floor_p) Rv = make_float2(P.x / mag, P.y / mag);
+        if (band && live && mag > floor_p) Rv = make_float2(P.x / mag, P.y / mag);
         o[lpad(g)] = Rv;
         if (band && !(same && col)) p.Rb[((long)pz * p.Ky + (sy + p.bky)) * p.Kx + ((col ? sx1 : sx0) + p.bkx)] = Rv;
     }
