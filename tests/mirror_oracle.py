@@ -21,14 +21,52 @@ def kmax(N, M, span):
     return int(min(N - 1, np.floor(float(N * M) / max(float(span), float(M)))))
 
 
-def mirror_matrix(N, M, origin, span):
-    """y = A x, A [M][N] real: the cosine form"""
+def table_kmax(N, M, span):
+    """what the plan reports and its tables are sized by (csrc/mirror_tables.hpp): the view rule of the doubled period,
+    min(N, floor(N M / max(span, M))) -- N itself only as the zero bin, so the cosines kept stop at kmax() above"""
+    return V.kmax(2 * N, M, span)
+
+
+def conv_length(N, M):
+    """the convolution length of a mirror axis: the smallest 2,3,5,7-smooth L >= 2N + M"""
+    return V.smooth_from(2 * N + M)
+
+
+def mirror_factors(N, M, origin, span):
+    """the two factors of the cosine form, A = E D: D [kmax + 1][N] the DCT-II's rows, E [M][kmax + 1] the cosines at the positions
+    (for lengths of thousands: E (D x) in place of forming A)"""
     k = np.arange(kmax(N, M, span) + 1)
     t = V.positions(M, origin, span)
     g = np.where(k == 0, 1.0, 2.0) / N
     E = np.cos(np.pi * np.outer(2 * t + 1, k) / (2 * N)) * g                   # [M][kmax + 1]
     D = np.cos(np.pi * np.outer(k, 2 * np.arange(N) + 1) / (2 * N))            # [kmax + 1][N]: the DCT-II
+    return E, D
+
+
+def mirror_matrix(N, M, origin, span):
+    """y = A x, A [M][N] real: the cosine form"""
+    E, D = mirror_factors(N, M, origin, span)
     return E @ D
+
+
+def chirp_tables(N, M, origin, span):
+    """the chirp-z factorisation the kernels run (csrc/mirror_tables.hpp) in longdouble: the periodic view's tables
+    (view_oracle.chirp_tables) of the period 2N aimed at origin + 1/2, the sum formed in longdouble (exact)"""
+    return V.chirp_tables(2 * N, M, np.longdouble(origin) + np.longdouble(0.5), span)
+
+
+def mirror_1d_chirp(x, M, origin, span):
+    """the amplitude-preserving y through that factorisation (direct convolution), Z_j = 2 C[|j - kmax|] with C[N] = 0: for the
+    comparison with mirror_matrix"""
+    x = np.asarray(x, dtype=np.float64)
+    N = len(x)
+    k, pre, post, c = chirp_tables(N, M, origin, span)
+    K = 2 * k + 1
+    Cc = np.append(dct2(x), 0.0)
+    Z = 2 * Cc[np.abs(np.arange(K) - k)] * pre.astype(np.complex128)
+    c = c.astype(np.complex128)
+    y = np.array([np.sum(Z * c[(m - np.arange(K)) + (K - 1)]) for m in range(M)])
+    return y * post.astype(np.complex128) * (M / float(span))
 
 
 def extend(x, axis=-1):

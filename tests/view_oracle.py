@@ -18,19 +18,43 @@ def kmax(N, M, span):
     return int(min(N // 2, np.floor(float(N * M) / (2.0 * max(float(span), float(M))))))
 
 
+def smooth_from(n):
+    """the smallest 2,3,5,7-smooth length >= n"""
+    def smooth(q):
+        for p in (2, 3, 5, 7):
+            while q % p == 0:
+                q //= p
+        return q == 1
+    while not smooth(n):
+        n += 1
+    return n
+
+
+def conv_length(N, M):
+    """the convolution length of an axis: the smallest 2,3,5,7-smooth L >= 2 (N // 2) + M (the worst case kmax = N // 2)"""
+    return smooth_from(2 * (N // 2) + M)
+
+
 def positions(M, origin, span):
     """input positions of the M output pixels"""
     return float(origin) + np.arange(M) * (float(span) / M)
 
 
-def view_matrix(N, M, origin, span):
-    """y = V x, V [M][N] complex (real up to rounding: the tests check that)"""
+def view_factors(N, M, origin, span):
+    """the two factors of the dense statement, V = E F / N: E [M][K] evaluates the kept bins at the positions, F [K][N] is the
+    DFT's rows of those bins (for lengths of thousands, where E (F x) / N costs a thousandth of forming V)"""
     k = kmax(N, M, span)
     f = np.arange(-k, k + 1)
     g = np.where(2 * np.abs(f) == N, 0.5, 1.0)
     t = positions(M, origin, span)
     E = np.exp(2j * np.pi * np.outer(t, f) / N) * g                    # [M][K]
     F = np.exp(-2j * np.pi * np.outer(f, np.arange(N)) / N)            # [K][N]: X[f mod N] = sum_n x[n] exp(-2 pi i nf / N)
+    return E, F
+
+
+def view_matrix(N, M, origin, span):
+    """y = V x, V [M][N] complex (real up to rounding: the tests check that)"""
+    E, F = view_factors(N, M, origin, span)
     return E @ F / N
 
 
