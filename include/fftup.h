@@ -586,6 +586,52 @@ FFTUP_API int fftup_align_get_info(const fftup_align* a, fftup_align_info* info)
 FFTUP_API int fftup_align_shifts(fftup_align* a, const fftup_device_image* ref, const fftup_device_image* cur,
                                  uint32_t n_pairs, fftup_shift* shifts_device, void* stream /* hipStream_t; NULL = the default stream */);
 
+/* EXTENSION: views moved by shifts in DEVICE memory -- the estimates above reach the views without a host copy.
+ * fftup_execute_device_views_shifted is fftup_execute_device_views with ONE change: frame i is computed at views[i] with its origin
+ * moved by (dx, dy) of shifts_device[i].  The shift is read on the GPU, by the frame's own table kernel (view_tables) when it runs;
+ * the host never reads it and never waits for it, so the output of fftup_align_shifts or fftup_shift_path enqueued on `stream`
+ * before this call is consumed without a synchronisation: all of the call's work starts after everything enqueued on `stream`
+ * before the call, as for fftup_execute_device.
+ * Per axis origin_i = views[i].origin + (double)shift -- ONE IEEE double addition of the fp32 value widened to double -- and the
+ * tables follow from origin_i by the arithmetic of csrc/view_phase.hpp as for any view.  A dx or dy that is not finite counts as 0
+ * on that axis, independently of the other axis; peak and peak_coarse are not read.  Everything the host derives from a view
+ * (the bins and spectrum columns kept, the sharpen constant, which tables a lane rebuilds, the rules of fftup_plan_set_view) depends
+ * on the span alone and is taken from views[i]: no shift can break a rule.  The result is byte for byte what
+ * fftup_execute_device_views gives for views whose origins the host moved by the same fp32 shifts in double.
+ * The caller keeps shifts_device alive and unwritten until `stream` has passed the call; exactly n_frames * sizeof(fftup_shift)
+ * bytes are read there, nothing is written.  The plan's own view, fftup_plan_set_view, fftup_plan_describe, fftup_plan_info and the
+ * slot paths stay as they are; fftup_download_view_tables returns what the lane last built, the shift included.
+ * FFTUP_E_INVALID_ARG, before anything is enqueued: everything fftup_execute_device_views refuses; shifts_device null, not a
+ * multiple of 4, or not device memory of the plan's device.
+ * Detect the feature by this symbol; fftup_version() and FFTUP_ABI_VERSION are unchanged. */
+FFTUP_API int fftup_execute_device_views_shifted(fftup_plan* plan, const fftup_device_image* in, const fftup_device_image* out,
+                                                 const fftup_view* views, const fftup_shift* shifts_device,
+                                                 uint32_t n_frames, void* stream);
+
+/* EXTENSION: a smoothed camera path -- the second half of a stabiliser.  fftup_shift_path turns n_frames measured shifts into the
+ * view offsets that follow a low-passed camera path instead of locking every frame on the reference: ONE kernel (shift_path, one
+ * workgroup) on `stream`, asynchronous, no allocation, no host read; the device is the one the pointers belong to.
+ * out_device == in_device is allowed (every input is read before anything is written).  No atomics: the same call gives the same
+ * bytes.  All arithmetic in fp64, per axis, i = 0 .. n_frames - 1 (csrc/shift_path.hpp; tests/path_oracle.py restates it):
+ *   frame i is MEASURED when in[i].peak >= min_peak (a NaN peak is not) and in[i].dx, in[i].dy are both finite.
+ *   FFTUP_PATH_ABSOLUTE: in[i] is frame i against one fixed reference.  p[i] = in[i] if measured, else p[i - 1]; p[-1] = 0.
+ *   FFTUP_PATH_CONSECUTIVE: in[i] is frame i against frame i - 1.  p[0] = 0 (in[0] is ignored whatever it holds),
+ *     p[i] = p[i - 1] + in[i] if measured, else p[i - 1].
+ *   The target path s: sigma == 0: s = 0 -- every frame locked on the reference.  Otherwise r = ceil(3 sigma),
+ *     g[j] = exp(-j^2 / (2 sigma^2)), s[i] = sum_{|j| <= r} g[j] p[clamp(i + j, 0, n_frames - 1)] / sum_{|j| <= r} g[j].
+ *   out[i].dx, out[i].dy = (float)(p[i] - s[i]), one rounding; out[i].peak and out[i].peak_coarse are in[i]'s, bit for bit.
+ * Sign: cur(x) ~ ref(x - d), so frame i shows at origin + p[i] what frame 0 shows at origin, and at origin + p[i] - s[i] it follows
+ * the smoothed camera: the offsets are what fftup_execute_device_views_shifted takes.  A path that is smooth already (p linear, away
+ * from the clip's ends) gets offsets of 0.
+ * FFTUP_E_INVALID_ARG (fftup_last_error names the rule), before anything is enqueued: a null pointer; n_frames == 0 or above
+ * FFTUP_PATH_MAX_FRAMES; mode > 1; sigma negative, not finite or above 256; min_peak not finite; in_device or out_device not a
+ * multiple of 4, not device memory, or memory of two devices.
+ * Detect the feature by this symbol; fftup_version() and FFTUP_ABI_VERSION are unchanged. */
+enum { FFTUP_PATH_ABSOLUTE = 0, FFTUP_PATH_CONSECUTIVE = 1, FFTUP_PATH_MAX_FRAMES = 4096 };
+typedef struct fftup_path_config { uint32_t mode; float sigma; float min_peak; } fftup_path_config;
+FFTUP_API int fftup_shift_path(const fftup_path_config* cfg, const fftup_shift* in_device, fftup_shift* out_device,
+                               uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
+
 FFTUP_API const char* fftup_strerror(int code);
 FFTUP_API const char* fftup_last_error(void);   /* thread-local detail of the last failure */
 FFTUP_API const char* fftup_version(void);

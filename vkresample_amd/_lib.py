@@ -30,6 +30,11 @@ ALIGN_CENTRE = 1                  # pixel centres aligned: output pixel m at inp
 FMT_RGB8 = 0                      # interleaved 8-bit RGB, rows of row_stride_bytes
 FMT_PLANAR = 1                    # 3 planes in the plan's storage type
 
+# fftup_path_config.mode (fftup_shift_path)
+PATH_ABSOLUTE = 0                 # in[i]: frame i against one fixed reference
+PATH_CONSECUTIVE = 1              # in[i]: frame i against frame i - 1 (in[0] is ignored)
+PATH_MAX_FRAMES = 4096
+
 # every symbol include/fftup.h declares
 EXPORTS = [
     "fftup_device_count", "fftup_device_name", "fftup_plan_create", "fftup_plan_destroy", "fftup_plan_info",
@@ -42,6 +47,7 @@ EXPORTS = [
     "fftup_stream_create", "fftup_stream_destroy", "fftup_plan_create_view", "fftup_plan_set_view",
     "fftup_execute_device_views", "fftup_download_view_tables",
     "fftup_align_create", "fftup_align_destroy", "fftup_align_get_info", "fftup_align_shifts",
+    "fftup_execute_device_views_shifted", "fftup_shift_path",
 ]
 ABI_VERSION = 2
 
@@ -88,6 +94,11 @@ class AlignInfo(C.Structure):
     _fields_ = [("window_w", C.c_uint32), ("window_h", C.c_uint32), ("decimate", C.c_uint32), ("crop_x", C.c_uint32),
                 ("crop_y", C.c_uint32), ("upsample", C.c_uint32), ("band_kx", C.c_uint32), ("band_ky", C.c_uint32),
                 ("num_kernels", C.c_uint32), ("device_bytes", C.c_uint64), ("kernel_names", (C.c_char * 64) * 8)]
+
+
+class PathConfig(C.Structure):
+    """fftup_path_config"""
+    _fields_ = [("mode", C.c_uint32), ("sigma", C.c_float), ("min_peak", C.c_float)]
 
 
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
@@ -161,5 +172,7 @@ def load():
     lib.fftup_align_destroy.restype = None
     lib.fftup_align_get_info.argtypes = [vp, C.POINTER(AlignInfo)]
     lib.fftup_align_shifts.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp, vp]
+    lib.fftup_execute_device_views_shifted.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(View), vp, u32, vp]
+    lib.fftup_shift_path.argtypes = [C.POINTER(PathConfig), vp, vp, u32, vp]
     _libs[path] = lib
     return lib

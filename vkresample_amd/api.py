@@ -270,6 +270,21 @@ class Upscaler:
         s = stream.handle if isinstance(stream, Stream) else stream
         _check(self._lib.fftup_execute_device_views(self._h, a, b, c, len(ins), s), "fftup_execute_device_views")
 
+    def execute_device_views_shifted(self, inputs, outputs, views, shifts_ptr, stream=None):
+        """execute_device_views with frame i's origin moved by (dx, dy) of the i-th fftup_shift at `shifts_ptr`, DEVICE memory
+        (fftup_execute_device_views_shifted): the GPU reads the shifts when the frame's tables are built, so what
+        Aligner.shifts_device or shift_path enqueued on `stream` before is consumed without a host copy or wait."""
+        ins = [inputs] if isinstance(inputs, DeviceImage) else list(inputs)
+        outs = [outputs] if isinstance(outputs, DeviceImage) else list(outputs)
+        vws = list(views)
+        if not len(ins) == len(outs) == len(vws):
+            raise ValueError("execute_device_views_shifted: %d inputs, %d outputs, %d views" % (len(ins), len(outs), len(vws)))
+        a = (_lib.DeviceImageDesc * len(ins))(*[i.desc() for i in ins])
+        b = (_lib.DeviceImageDesc * len(outs))(*[o.desc() for o in outs])
+        c = (_lib.View * len(vws))(*[_lib.View(o[0], o[1], sp[0], sp[1]) for (o, sp) in vws])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_execute_device_views_shifted(self._h, a, b, c, shifts_ptr, len(ins), s), "fftup_execute_device_views_shifted")
+
     def download_view_tables(self, lane, axis):
         """The chirp tables lane `lane` last built for axis 0 (x) or 1 (y) in execute_device_views (fftup_download_view_tables, a
         test tap): (kmax, pre, post, bhat), complex64 arrays of 2 kmax + 1, out length and L points."""
@@ -426,6 +441,20 @@ def stabilised_views(view, shifts):
     so it shows what the reference frame shows at the origin.  view: (origin, span); shifts: rows of Aligner.shifts (or (dx, dy) pairs)."""
     (ox, oy), span = view
     return [((float(ox) + float(s[0]), float(oy) + float(s[1])), (float(span[0]), float(span[1]))) for s in shifts]
+
+
+PATH_ABSOLUTE, PATH_CONSECUTIVE, PATH_MAX_FRAMES = _lib.PATH_ABSOLUTE, _lib.PATH_CONSECUTIVE, _lib.PATH_MAX_FRAMES
+
+
+def shift_path(in_ptr, out_ptr, n, mode=PATH_CONSECUTIVE, sigma=0.0, min_peak=0.0, stream=None):
+    """Measured shifts -> the view offsets of a smoothed camera path (fftup_shift_path): `n` fftup_shift at `in_ptr`, device memory
+    (PATH_ABSOLUTE: each against one reference; PATH_CONSECUTIVE: each against the frame before), accumulated into the path p,
+    low-passed by a Gaussian of `sigma` frames into s, and p - s written as dx, dy to `out_ptr` (may be `in_ptr`) -- what
+    Upscaler.execute_device_views_shifted takes.  sigma = 0: every frame locked on the reference.  Frames with peak < min_peak hold
+    the path.  Asynchronous: one kernel on `stream`, nothing waits here."""
+    cfg = _lib.PathConfig(mode, sigma, min_peak)
+    s = stream.handle if isinstance(stream, Stream) else stream
+    _check(_lib.load().fftup_shift_path(C.byref(cfg), in_ptr, out_ptr, n, s), "fftup_shift_path")
 
 
 class PinnedArray:

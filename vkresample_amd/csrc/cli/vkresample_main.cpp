@@ -27,7 +27,10 @@
 //   -viewto ox,oy,sx,sy -frames K  with -size and -view: one image, K frames whose view moves from -view to -viewto, in ONE
 //                 fftup_execute_device_views call on device buffers; K files, -o NAME.png -> NAME_0001.png ...
 //   -stabilise    batched mode with -size [-view] [-mirror]: fftup_align_shifts estimates every frame's shift against frame 000001,
-//                 fftup_execute_device_views shows each frame at the view moved by its shift
+//                 fftup_execute_device_views_shifted shows each frame at the view moved by its shift, read from device memory
+//   -smooth SIGMA [-minpeak P]  with -stabilise: follow a smoothed camera path instead of locking on frame 000001 -- the shifts are
+//                 estimated between consecutive frames, fftup_shift_path (Gaussian of SIGMA frames; frames with a peak below P hold
+//                 the path) turns them into view offsets on the GPU, and the frame lines gain ` offset ox oy`
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -71,6 +74,8 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     uint32_t frames = 0;                     // -viewto ox,oy,sx,sy -frames K: a clip of K views from `view` to `viewTo` (0: none)
     fftup_view viewTo{};
     bool stabilise = false;                  // -stabilise: batched mode, every frame shown where frame 000001 shows the view
+    bool smooth = false;                     // -smooth SIGMA: ... where a smoothed camera path shows it (fftup_shift_path)
+    float smoothSigma = 0.f, minPeak = 0.f;  // -minpeak P
 };
 
 // frame k of the K views of a move from a to b, t = k / (K - 1): per axis the origin linear in t, the span geometric; the ends exact
@@ -137,8 +142,11 @@ static int run_view_clip(const ResampleConfiguration& config, fftup_plan* plan, 
 }
 
 // -stabilise: a folder of frames, frame 000001 the reference.  Every frame goes to device memory once; fftup_align_shifts estimates
-// each frame's shift against the reference (one call, the aligner batches); fftup_execute_device_views renders frame k at the view's
-// origin + its shift, so every output shows what the reference shows; one "frame %06d: shift dx dy peak p" line per frame
+// each frame's shift against the reference (one call, the aligner batches); fftup_execute_device_views_shifted renders frame k at
+// the view's origin + its shift, read by the GPU from the aligner's result, so every output shows what the reference shows; one
+// "frame %06d: shift dx dy peak p" line per frame, from a copy made behind the render call.  -smooth: the pairs are (frame k - 1,
+// frame k), one fftup_shift_path between the estimates and the render turns them into the offsets of a smoothed path -- the lines
+// gain " offset ox oy".  Estimates, path and render are enqueued on one stream with no host wait between them
 static int run_stabilise(const ResampleConfiguration& config)
 {
     const int N = config.numFiles;
@@ -171,31 +179,40 @@ static int run_stabilise(const ResampleConfiguration& config)
     void* din = res == FFTUP_OK ? fftup_device_alloc(config.device_id, inBytes * N) : nullptr;
     void* dout = res == FFTUP_OK ? fftup_device_alloc(config.device_id, outBytes * N) : nullptr;
     void* dshift = res == FFTUP_OK ? fftup_device_alloc(config.device_id, sizeof(fftup_shift) * N) : nullptr;
-    if (res == FFTUP_OK && !(din && dout && dshift)) res = FFTUP_E_OUT_OF_MEMORY;
-    std::vector<fftup_shift> shifts((size_t)N);
+    void* doffset = res == FFTUP_OK && config.smooth ? fftup_device_alloc(config.device_id, sizeof(fftup_shift) * N) : nullptr;
+    if (res == FFTUP_OK && !(din && dout && dshift && (doffset || !config.smooth))) res = FFTUP_E_OUT_OF_MEMORY;
+    std::vector<fftup_shift> shifts((size_t)N), offsets((size_t)N);
     std::vector<uint8_t> host(res == FFTUP_OK ? outBytes * N : 0);
     if (res == FFTUP_OK) res = fftup_device_copy(din, frames.data(), inBytes * N, 0, nullptr);
     if (res == FFTUP_OK) {
         std::vector<fftup_device_image> ref((size_t)N), in((size_t)N), out((size_t)N);
         for (int f = 0; f < N; f++) {
-            ref[f] = {din, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            ref[f] = {(uint8_t*)din + (config.smooth && f ? inBytes * (f - 1) : 0), FFTUP_FMT_RGB8, (size_t)width * 3, 0};
             in[f] = {(uint8_t*)din + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
             out[f] = {(uint8_t*)dout + outBytes * f, FFTUP_FMT_RGB8, (size_t)uW * 3, 0};
         }
         res = fftup_align_shifts(aligner, ref.data(), in.data(), (uint32_t)N, (fftup_shift*)dshift, nullptr);
-        if (res == FFTUP_OK) res = fftup_device_copy(shifts.data(), dshift, sizeof(fftup_shift) * N, 1, nullptr);   // (ordered behind the estimates, blocking)
-        std::vector<fftup_view> views((size_t)N, view);
-        for (int f = 0; f < N && res == FFTUP_OK; f++) {
-            views[f].origin_x += (double)shifts[f].dx;
-            views[f].origin_y += (double)shifts[f].dy;
-            printf("frame %06d: shift %.3f %.3f peak %.3f\n", f + 1, shifts[f].dx, shifts[f].dy, shifts[f].peak);
+        if (res == FFTUP_OK && config.smooth) {
+            const fftup_path_config pcfg{FFTUP_PATH_CONSECUTIVE, config.smoothSigma, config.minPeak};
+            res = fftup_shift_path(&pcfg, (const fftup_shift*)dshift, (fftup_shift*)doffset, (uint32_t)N, nullptr);
         }
-        if (res == FFTUP_OK) res = fftup_execute_device_views(plan, in.data(), out.data(), views.data(), (uint32_t)N, nullptr);
+        const std::vector<fftup_view> views((size_t)N, view);
+        const fftup_shift* moved = (const fftup_shift*)(config.smooth ? doffset : dshift);
+        if (res == FFTUP_OK) res = fftup_execute_device_views_shifted(plan, in.data(), out.data(), views.data(), moved, (uint32_t)N, nullptr);
         if (res == FFTUP_OK) res = fftup_device_copy(host.data(), dout, outBytes * N, 1, nullptr);
+        // (for printing only, behind the render call)
+        if (res == FFTUP_OK) res = fftup_device_copy(shifts.data(), dshift, sizeof(fftup_shift) * N, 1, nullptr);
+        if (res == FFTUP_OK && config.smooth) res = fftup_device_copy(offsets.data(), doffset, sizeof(fftup_shift) * N, 1, nullptr);
+        for (int f = 0; f < N && res == FFTUP_OK; f++) {
+            printf("frame %06d: shift %.3f %.3f peak %.3f", f + 1, shifts[f].dx, shifts[f].dy, shifts[f].peak);
+            if (config.smooth) printf(" offset %.3f %.3f", offsets[f].dx, offsets[f].dy);
+            printf("\n");
+        }
     }
     fftup_device_free(din);
     fftup_device_free(dout);
     fftup_device_free(dshift);
+    fftup_device_free(doffset);
     fftup_align_destroy(aligner);
     fftup_plan_destroy(plan);
     if (res != FFTUP_OK) {
@@ -532,6 +549,7 @@ int main(int argc, char* argv[])
         printf("	-mirror: with -size and -view: continue the image by its reflection instead of periodically: no wrap-around at the borders, e.g. -size 1920x1080 -view -0.144,-0.144,1366,768 -mirror -anysize on 1366x768 (-p 0 and -p 2, not with -dct)\n");
         printf("	-viewto OX,OY,SX,SY -frames K: with -size and -view, single image mode: a clip of K frames (2 to 9999) whose view moves from -view to -viewto (position linear, span geometric); -o NAME.png gives NAME_0001.png ...; the views are printed, one 'view k: ox oy sx sy' line each\n");
         printf("	-stabilise: batched mode with -size [-view] [-mirror]: frame 000001 is the reference; every frame's shift against it is estimated on the GPU (phase correlation) and the frame is shown at the view moved by that shift; one 'frame N: shift dx dy peak p' line each; one thread, one device\n");
+        printf("	-smooth SIGMA [-minpeak P]: with -stabilise: follow a smoothed camera path instead of locking on frame 000001: shifts between consecutive frames, accumulated and low-passed on the GPU by a Gaussian of SIGMA frames (0 to 256; 0 locks on frame 000001); frames whose peak is below P hold the path; the frame lines gain ' offset ox oy'; at most 4096 frames\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -625,6 +643,25 @@ int main(int argc, char* argv[])
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");
     config.stabilise = findFlag(B, E, "-stabilise");
+    if (findFlag(B, E, "-smooth")) {
+        char* v = getFlagValue(B, E, "-smooth");
+        char tail = 0;
+        if (!config.stabilise) { printf("-smooth smooths the path of -stabilise: it cannot be used without it\n"); return 1; }
+        if (!v || sscanf(v, "%f%c", &config.smoothSigma, &tail) != 1 || !(config.smoothSigma >= 0.f && config.smoothSigma <= 256.f)) {
+            printf("No proper width is selected with -smooth flag (frames, a number from 0 to 256)\n");
+            return 1;
+        }
+        config.smooth = true;
+    }
+    if (findFlag(B, E, "-minpeak")) {
+        char* v = getFlagValue(B, E, "-minpeak");
+        char tail = 0;
+        if (!config.smooth) { printf("-minpeak sets which frames -smooth trusts: it cannot be used without it\n"); return 1; }
+        if (!v || sscanf(v, "%f%c", &config.minPeak, &tail) != 1 || !std::isfinite(config.minPeak)) {
+            printf("No proper peak is selected with -minpeak flag (a number, e.g. 0.1)\n");
+            return 1;
+        }
+    }
     if (config.stabilise) {
         // what the mode cannot serve: one line, exit code 1
         if (findFlag(B, E, "-i") || !findFlag(B, E, "-ifolder")) { printf("-stabilise works on a folder of frames (-ifolder, -ofolder, -numfiles): it cannot be combined with -i\n"); return 1; }

@@ -1,6 +1,7 @@
 // fftup_align.hip -- shift estimates: the aligner object of include/fftup.h (fftup_align_create / _destroy / _get_info / _shifts) and the
 // launches of its kernels (kernels_align.hpp).  The geometry comes from align_geometry (plan_rules.cpp), before any device access;
 // tables and the buffers of max_batch pairs are made at creation; fftup_align_shifts validates, then only launches.
+// And fftup_shift_path, which needs no aligner: measured shifts -> the view offsets of a smoothed camera path (shift_path.hpp).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -13,6 +14,7 @@
 
 #include "kernels_align.hpp"
 #include "plan.hpp"
+#include "shift_path.hpp"
 
 using namespace fftup;
 
@@ -210,6 +212,39 @@ int fftup_align_shifts(fftup_align* a, const fftup_device_image* ref, const fftu
         if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("fftup_align_shifts: kernel launch: ") + hipGetErrorString(e));
     }
     return FFTUP_OK;
+}
+
+// measured shifts -> the view offsets of a smoothed camera path (shift_path.hpp has the definition): the rules on the numbers first,
+// before any device access; then the pointers, whose attributes name the device; then one launch
+int fftup_shift_path(const fftup_path_config* cfg, const fftup_shift* in_device, fftup_shift* out_device, uint32_t n_frames, void* stream)
+{
+    if (!cfg) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: cfg is null");
+    if (!in_device) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: in_device is null");
+    if (!out_device) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: out_device is null");
+    if (n_frames == 0) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: n_frames must be > 0");
+    if (n_frames > (uint32_t)FFTUP_PATH_MAX_FRAMES)
+        return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: n_frames " + std::to_string(n_frames) + " is above FFTUP_PATH_MAX_FRAMES (" + std::to_string((int)FFTUP_PATH_MAX_FRAMES) + ")");
+    if (cfg->mode > 1) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: mode must be FFTUP_PATH_ABSOLUTE (0) or FFTUP_PATH_CONSECUTIVE (1)");
+    if (!(std::isfinite(cfg->sigma) && cfg->sigma >= 0.0f && cfg->sigma <= fftup_shiftpath::MAX_SIGMA))
+        return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: sigma must be a finite number in [0, 256]");
+    if (!std::isfinite(cfg->min_peak)) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: min_peak must be a finite number");
+    int device = -1;
+    const struct { const void* p; const char* name; } ptrs[2] = {{in_device, "in_device"}, {out_device, "out_device"}};
+    for (const auto& q : ptrs) {
+        const std::string at = std::string("fftup_shift_path: ") + q.name;
+        if ((uintptr_t)q.p % sizeof(float)) return fail(FFTUP_E_INVALID_ARG, at + " is not a multiple of 4 bytes");
+        hipPointerAttribute_t a{};
+        const hipError_t e = hipPointerGetAttributes(&a, q.p);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FFTUP_E_INVALID_ARG, at + " is not device memory (hipPointerGetAttributes: " + hipGetErrorString(e) + ")");
+        }
+        if (a.type != hipMemoryTypeDevice) return fail(FFTUP_E_INVALID_ARG, at + " is not device memory");
+        if (device >= 0 && a.device != device) return fail(FFTUP_E_INVALID_ARG, "fftup_shift_path: in_device and out_device are not memory of one and the same device");
+        device = a.device;
+    }
+    HIP_TRY(hipSetDevice(device));
+    return launch_shift_path(in_device, out_device, n_frames, cfg->mode, cfg->sigma, cfg->min_peak, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -91,8 +91,11 @@ int ensure_events(fftup_plan* P)
     return FFTUP_OK;
 }
 
-// fftup_execute_device, and with `views` fftup_execute_device_views: frame i computed with views[i] instead of the plan's view
-int execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views, uint32_t n_frames, void* stream)
+// fftup_execute_device, and with `views` fftup_execute_device_views: frame i computed with views[i] instead of the plan's view;
+// with `shifts` as well fftup_execute_device_views_shifted (`who` names the entry point): frame i's table kernel moves the origin of
+// views[i] by shifts[i] in device memory -- checked here as fftup_align_shifts checks its own shifts_device, never read here
+int execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views, const fftup_shift* shifts,
+                   const char* who, uint32_t n_frames, void* stream)
 {
     if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
     if (!in || !out) return fail(FFTUP_E_INVALID_ARG, "null image array");
@@ -102,8 +105,19 @@ int execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_devi
     for (uint32_t i = 0; i < n_frames; i++) {
         int rc = check_image(P, in[i], "in", i, P->W, P->H, false);
         if (!rc) rc = check_image(P, out[i], "out", i, P->uW, P->uH, true);
-        if (!rc && views) rc = check_view(("fftup_execute_device_views: views[" + std::to_string(i) + "]").c_str(), &views[i], P->uW, P->uH);
+        if (!rc && views) rc = check_view((std::string(who) + ": views[" + std::to_string(i) + "]").c_str(), &views[i], P->uW, P->uH);
         if (rc) return rc;
+    }
+    if (shifts) {
+        if ((uintptr_t)shifts % sizeof(float)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": shifts_device is not a multiple of 4 bytes");
+        hipPointerAttribute_t at{};
+        const hipError_t e = hipPointerGetAttributes(&at, shifts);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": shifts_device is not device memory (hipPointerGetAttributes: " + hipGetErrorString(e) + ")");
+        }
+        if (at.type != hipMemoryTypeDevice || at.device != P->device)
+            return fail(FFTUP_E_INVALID_ARG, std::string(who) + ": shifts_device is not device memory of the plan's device");
     }
     int rc = ensure_events(P);
     if (rc) return rc;
@@ -135,7 +149,7 @@ int execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_devi
                                   P->W * esz, P->H, 3, 1, st);             // (the source is not element aligned: bytes)
             io.in = stage; io.kind = 1; io.in_row = (long)P->W; io.in_plane = (long)P->in_plane_stride;
         }
-        const FrameRun r{l, 0, ro.in_place ? dst.data : P->dio.scratch_out[l], &io, Pass::all, views ? &views[i] : nullptr};
+        const FrameRun r{l, 0, ro.in_place ? dst.data : P->dio.scratch_out[l], &io, Pass::all, views ? &views[i] : nullptr, shifts ? &shifts[i] : nullptr};
         if ((rc = launch_frame(P, r))) break;
         if (!ro.in_place) {
             if (dst.format == FFTUP_FMT_PLANAR)
@@ -161,7 +175,7 @@ extern "C" {
 
 int fftup_execute_device(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, uint32_t n_frames, void* stream)
 {
-    return execute_device(P, in, out, nullptr, n_frames, stream);
+    return execute_device(P, in, out, nullptr, nullptr, "fftup_execute_device", n_frames, stream);
 }
 
 int fftup_execute_device_views(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views,
@@ -170,7 +184,17 @@ int fftup_execute_device_views(fftup_plan* P, const fftup_device_image* in, cons
     if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
     if (!views) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views: views is null");
     if (!P->view) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views: not a view plan (fftup_plan_create_view makes one)");
-    return execute_device(P, in, out, views, n_frames, stream);
+    return execute_device(P, in, out, views, nullptr, "fftup_execute_device_views", n_frames, stream);
+}
+
+int fftup_execute_device_views_shifted(fftup_plan* P, const fftup_device_image* in, const fftup_device_image* out, const fftup_view* views,
+                                       const fftup_shift* shifts_device, uint32_t n_frames, void* stream)
+{
+    if (!P) return fail(FFTUP_E_INVALID_ARG, "null plan");
+    if (!views) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views_shifted: views is null");
+    if (!shifts_device) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views_shifted: shifts_device is null");
+    if (!P->view) return fail(FFTUP_E_INVALID_ARG, "fftup_execute_device_views_shifted: not a view plan (fftup_plan_create_view makes one)");
+    return execute_device(P, in, out, views, shifts_device, "fftup_execute_device_views_shifted", n_frames, stream);
 }
 
 // the parity tests' tap: the tables lane `lane` last built for axis 0 (x) or 1 (y)

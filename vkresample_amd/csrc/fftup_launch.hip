@@ -30,6 +30,7 @@
 #include "kernels_view.hpp"
 #include "kernels_mirror.hpp"
 #include "kernels_view_tables.hpp"
+#include "kernels_path.hpp"
 #include "kernels_device_io.hpp"
 #include "mirror_tables.hpp"
 
@@ -840,7 +841,9 @@ int kernels_allow_view_tables(const fftup_plan* P)
     if (allow.err != hipSuccess) return fail(FFTUP_E_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(allow.err));
     return FFTUP_OK;
 }
-static void frame_view(fftup_plan* P, int lane, const fftup_view& v, Frame& f)
+// shift: the frame's fftup_shift in device memory (fftup_execute_device_views_shifted; nullptr: none) -- k_view_tables moves the
+// origins by its dx, dy when it runs; nothing the host derives here depends on the origin
+static void frame_view(fftup_plan* P, int lane, const fftup_view& v, const fftup_shift* shift, Frame& f)
 {
     fftup_plan::ViewTabs& t = P->vtabs[lane];
     struct Ax { const fftup_plan::ViewAxis* a; uint32_t N, M; double o, sp; ViewTables* out; };
@@ -854,6 +857,7 @@ static void frame_view(fftup_plan* P, int lane, const fftup_view& v, Frame& f)
         q.chirp = t.span[i] != x.sp;
         const fftup_viewphase::Pair o = fftup_viewphase::origin_of(x.o, (double)q.n, P->mirror);
         q.o_hi = o.hi; q.o_lo = o.lo; q.span = x.sp; q.plan = x.a->planL; q.tw = P->vroots[i];
+        q.origin = x.o; q.mirror = P->mirror ? 1 : 0; q.shift = shift ? (i ? &shift->dy : &shift->dx) : nullptr;
         q.pre = t.pre[i]; q.post = t.post[i]; q.bhat = t.bhat[i];
         t.span[i] = x.sp; t.kmax[i] = q.kmax;
         *x.out = {q.kmax, q.pre, q.post, q.bhat};
@@ -884,13 +888,26 @@ int launch_frame(fftup_plan* P, const FrameRun& r)
     if (f.kind == 0 && !tap) return fail(FFTUP_E_NO_INPUT, "no input uploaded for this slot");     // (the tap reads spectra only)
     if (r.view) {
         if (P->family != Family::view || (size_t)r.lane >= P->vtabs.size() || !P->vtabs[r.lane].pre[0]) return fail(FFTUP_E_INVALID_ARG, "a frame with a view of its own: not a view plan, or its lane has no tables");
-        frame_view(P, r.lane, *r.view, f);
+        frame_view(P, r.lane, *r.view, r.shift, f);
     }
     const int rc = launch_family(P, f, r.pass);
     if (rc && r.view) P->vtabs[r.lane].span[0] = P->vtabs[r.lane].span[1] = 0;      // (a failed launch: the lane's chirp tables are nobody's)
     // what the frame left: its inverse rows have run, so the tap reads this lane's spectra, or its R unless the fused kernel ran instead
     if (tap || runs(r.pass, Pass::inverse)) { P->last_lane = r.lane; P->R_valid = !(P->fused && !tap); }
     return rc;
+}
+
+// ---- fftup_shift_path: one workgroup; the path of 4096 frames alone is 64 KB of LDS, so the kernel is allowed what this call needs
+int launch_shift_path(const fftup_shift* in, fftup_shift* out, uint32_t n, uint32_t mode, float sigma, float min_peak, hipStream_t st)
+{
+    const Kern<ShiftPathParams> k = kern(k_shift_path, SP_THREADS, shift_path_lds((int)n, fftup_shiftpath::radius_of((double)sigma)));
+    AllowLds allow;
+    allow(k);
+    if (allow.err != hipSuccess) return fail(FFTUP_E_HIP, std::string("hipFuncSetAttribute(hipFuncAttributeMaxDynamicSharedMemorySize): ") + hipGetErrorString(allow.err));
+    launch(k, dim3(1), st, ShiftPathParams{(const float*)in, (float*)out, (int32_t)n, mode, sigma, min_peak});
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(FFTUP_E_HIP, std::string("fftup_shift_path: kernel launch: ") + hipGetErrorString(e));
+    return FFTUP_OK;
 }
 
 // 64-bit wrapping sum of 32-bit words (fftup_output_checksum): per-thread partial sums, wave reduction, one atomic per wave

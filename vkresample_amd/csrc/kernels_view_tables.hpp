@@ -12,6 +12,8 @@
 // fft_lds_inplace<+1, VT_PT> on VT_THREADS threads holds every smooth L up to 14336 (stage_fits_inplace; the radix-7 stage is the
 // tightest), above the 9637 points that fit the LDS.  The fp64 L-th roots are a table per axis the plan uploads once.
 // A pan (chirp == 0) rebuilds `pre` alone, the one table the origin enters.
+// fftup_execute_device_views_shifted: the origin is moved by a float the kernel reads from device memory when it runs -- the host
+// never sees it; everything else about the frame depends on the span alone and stays the host's.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,6 +31,11 @@ struct ViewTabAxis {
     int32_t kmax;
     int32_t chirp;           // 0: only `pre` is written
     double o_hi, o_lo, span; // the origin modulo n (mirror: + 1/2) as a pair (fftup_viewphase::origin_of, on the host)
+    // fftup_execute_device_views_shifted: the axis' float of the frame's fftup_shift in device memory (nullptr: none, o_hi / o_lo
+    // hold) -- the kernel moves `origin` by it and forms the pair itself, with the function the host forms o_hi / o_lo with
+    double origin;           // the view's origin as the caller gave it
+    int32_t mirror;
+    const float* shift;
     StagePlan plan;          // n = L
     const double2* tw;       // L-th roots in double, exp(+2 pi i k / L)
     float2* pre;             // 2 kmax + 1 points
@@ -44,7 +51,12 @@ __global__ void __launch_bounds__(VT_THREADS) k_view_tables(ViewTabParams p)
     double2* c = (double2*)smem;
     const ViewTabAxis& x = p.ax[blockIdx.x];
     const int tid = threadIdx.x, T = blockDim.x;
-    const fftup_viewphase::Axis a = fftup_viewphase::axis_of((uint32_t)x.n, (uint32_t)x.M, {x.o_hi, x.o_lo}, x.span, x.kmax);
+    fftup_viewphase::Pair o{x.o_hi, x.o_lo};
+    if (x.shift) {                                             // (workgroup-uniform; a shift that is not finite counts as 0)
+        const float d = *x.shift;
+        o = fftup_viewphase::origin_of(x.origin + (std::isfinite(d) ? (double)d : 0.0), (double)x.n, x.mirror != 0);
+    }
+    const fftup_viewphase::Axis a = fftup_viewphase::axis_of((uint32_t)x.n, (uint32_t)x.M, o, x.span, x.kmax);
     const int K = 2 * x.kmax + 1;
     for (int j = tid; j < K; j += T) {
         const fftup_viewphase::Cplx w = fftup_viewphase::pre_of(a, j);

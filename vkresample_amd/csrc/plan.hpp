@@ -8,8 +8,8 @@
 //   fftup_execute.hip  upload / execute / download (performVulkanUpscale, VkResample.cpp:1249-1279, and the transfers)
 //   fftup_queue.hip    host-streamed frames: fftup_submit_rgb8 / fftup_wait / fftup_drain
 //   fftup_png.hip      the device-side PNG encoder's host side
-//   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views and the device / stream helpers
-//   fftup_align.hip    shift estimates: the aligner object (fftup_align_*), beside the plan, and the launches of kernels_align.hpp
+//   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views[_shifted] and the device / stream helpers
+//   fftup_align.hip    shift estimates: the aligner object (fftup_align_*), beside the plan, and the launches of kernels_align.hpp; fftup_shift_path
 //   jit.cpp            the plan-time compiler
 //   jit_choose.cpp     the plan-time chooser: which factorizations a specialised plan runs (no device)
 #pragma once
@@ -161,9 +161,13 @@ struct DeviceInput { const void* in = nullptr; int kind = 0; long in_row = 0, in
 // in_slot: the ring slot the frame reads (`in`: instead of the slot); out: the image its last kernel writes -- a slot's, an extra
 // one of fftup_execute, caller memory, a lane's scratch
 // view: the frame's own view (fftup_execute_device_views; nullptr: the plan's) -- its tables are built on the lane's stream first
+// shift: with `view`, the frame's fftup_shift in DEVICE memory (fftup_execute_device_views_shifted; nullptr: none): the table
+// kernel moves the view's origin by its dx, dy when it runs, the host never reads it
 struct FrameRun { int lane = 0; uint32_t in_slot = 0; void* out = nullptr; const DeviceInput* in = nullptr; Pass pass = Pass::all;
-                  const fftup_view* view = nullptr; };
+                  const fftup_view* view = nullptr; const fftup_shift* shift = nullptr; };
 int launch_frame(fftup_plan* P, const FrameRun& r);               // launches, then records what the frame left: the only writer of last_lane and R_valid (but see fftup_execute)
+// fftup_shift_path: k_shift_path (kernels_path.hpp) on the current device, allowed its dynamic LDS first; n, mode and sigma are the caller's, checked
+int launch_shift_path(const fftup_shift* in, fftup_shift* out, uint32_t n, uint32_t mode, float sigma, float min_peak, hipStream_t st);
 void launch_unpack(fftup_plan* P, uint32_t slot, hipStream_t st);                  // the host loop of VR:1636-1685 as a kernel
 void launch_pack(fftup_plan* P, uint32_t slot, uint8_t* dst, hipStream_t st);      // ... and of VR:1708-1748
 void launch_checksum(fftup_plan* P, uint32_t slot, hipStream_t st);                // 64-bit sum of the slot's words -> P->d_sum
