@@ -632,6 +632,69 @@ typedef struct fftup_path_config { uint32_t mode; float sigma; float min_peak; }
 FFTUP_API int fftup_shift_path(const fftup_path_config* cfg, const fftup_shift* in_device, fftup_shift* out_device,
                                uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
 
+/* EXTENSION: rotation by three shears -- camera roll, the other half of hand shake.  A ROTATOR is a small object beside the plan,
+ * like the aligner: fftup_rotate_frames turns frames in caller-owned device memory about a centre, and every resampling step is
+ * the exact trigonometric interpolant of the frame.  Detect the feature by these symbols; fftup_version() and FFTUP_ABI_VERSION
+ * are unchanged.
+ *
+ * Definition (tests/rotate_oracle.py restates it in fp64).  A frame of W x H pixels is periodic on both axes, as for every FFT
+ * plan here; pixel indices are coordinates.  For a rotation (angle theta in radians, centre (c_x, c_y)) let a = -tan(theta / 2)
+ * and b = sin(theta), both in double: R(theta) = Sx(a) Sy(b) Sx(a).
+ *   x-shear with coefficient a, for every row y of every plane: delta = a (y - c_y), X = DFT_W(row),
+ *     Y[f] = X[f] exp(-2 pi i f delta / W) for signed f with 2 |f| < W; for even W, Y[W/2] = X[W/2] cos(pi delta) -- real, as the
+ *     view plans treat an even length's Nyquist bin; the new row is IDFT_W(Y), normalised by 1 / W.
+ *   y-shear with coefficient b: the same on columns, delta = b (x - c_x), length H.
+ *   out = x-shear(a) of y-shear(b) of x-shear(a) of in.  The two intermediate images are fp32 for every input format.
+ * Meaning: content moves by the matrix [[cos theta, -sin theta], [sin theta, cos theta]] about the centre,
+ * out(p) ~ in(c + R(-theta)(p - c)).  With y pointing down, a positive theta turns the picture clockwise on screen.
+ * On odd lengths every factor is a unit phasor and a shear loses nothing: rotating by theta and then by -theta returns the frame
+ * up to rounding.  On even lengths the Nyquist rule keeps the rows real but is not unitary: that round trip does not return the
+ * Nyquist bins.
+ * Wrap-around: content whose path leaves the frame during one of the three shears wraps around and shows up at the opposite
+ * border, as with every periodic plan -- at large angles a good part of the frame.  Small angles plus the zoom of a stabilising
+ * view keep such pixels out of the picture.  There is no padded canvas.
+ *
+ * Formats.  Input: FFTUP_FMT_RGB8 (code / 255) or FFTUP_FMT_PLANAR in the rotator's precision (0 float, 2 IEEE half;
+ * 1: FFTUP_E_UNSUPPORTED_PRECISION).  Output: FFTUP_FMT_PLANAR in the same precision, one rounding from fp32, or FFTUP_FMT_RGB8
+ * as u8 = clamp(floor(255 x + 0.5), 0, 255) -- ROUND TO NEAREST, not the trunc(255 x) of fftup_download_rgb8 and the plans' final
+ * store: a rotation is an intermediate step, and with truncation theta = 0 would darken 8-bit frames by a code wherever the
+ * transforms' rounding falls below an integer.  PLANAR `data` may be any address (a multiple of the element size is faster).
+ *
+ * Geometry (arithmetic on the configuration, decided before any device access; fftup_last_error names the rule and the axis).
+ * FFTUP_E_UNSUPPORTED_SIZE: a width or height below 2, above 4096 (both kernels hold two LDS buffers of two interleaved sequences,
+ * 139 KB at 4096) or with a prime factor above 7 (a rotator has no Bluestein path); odd lengths are accepted, they have no
+ * Nyquist bin.  FFTUP_E_INVALID_ARG: max_batch above 64.
+ *
+ * Ordering, containment and validation of fftup_rotate_frames, as fftup_align_shifts: everything is enqueued on `stream`, the host
+ * is never synchronised, the descriptor and rotation arrays are read before the call returns.  Nothing is allocated in the call:
+ * two fp32 intermediates of max_batch frames are made at creation, a longer call runs in chunks, in stream order.  Three kernels
+ * per chunk (fftup_rotate_info.kernel_names).  Exactly the named pixels of out[i] are written: row padding, plane padding and
+ * guard bytes stay untouched.  out[i] may be in[i] (in place): the first pass has read the whole frame into the first
+ * intermediate before the third writes; any other overlap between images of one call is the caller's responsibility.  One host
+ * thread per rotator at a time.
+ * Validation happens before any launch: FFTUP_E_INVALID_ARG for null pointers, n_frames == 0, every descriptor rule of
+ * fftup_execute_device (format, strides, device memory of the rotator's device), an angle or centre that is not finite and
+ * |theta| > pi / 2 (larger angles are a transpose or a flip plus a small angle); fftup_last_error names the frame index and the
+ * rule. */
+typedef struct fftup_rotate_config {
+    uint32_t width, height;      /* the frames' size: each in [2, 4096] and 2,3,5,7-smooth */
+    uint32_t precision;          /* element type of FFTUP_FMT_PLANAR frames: 0 float, 2 IEEE half (1: FFTUP_E_UNSUPPORTED_PRECISION) */
+    int32_t  device;
+    uint32_t max_batch;          /* frames whose intermediates are held, at most 64; 0 = 4; longer calls run in chunks */
+} fftup_rotate_config;
+typedef struct fftup_rotation { double angle, centre_x, centre_y; } fftup_rotation;   /* radians; pixels */
+typedef struct fftup_rotate fftup_rotate;
+typedef struct fftup_rotate_info {
+    uint32_t width, height, num_kernels, max_batch;
+    uint64_t device_bytes;
+    char     kernel_names[4][64];
+} fftup_rotate_info;
+FFTUP_API int fftup_rotate_create(fftup_rotate** out, const fftup_rotate_config* cfg);
+FFTUP_API void fftup_rotate_destroy(fftup_rotate* r);
+FFTUP_API int fftup_rotate_get_info(const fftup_rotate* r, fftup_rotate_info* info);
+FFTUP_API int fftup_rotate_frames(fftup_rotate* r, const fftup_device_image* in, const fftup_device_image* out,
+                                  const fftup_rotation* rotations, uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
+
 FFTUP_API const char* fftup_strerror(int code);
 FFTUP_API const char* fftup_last_error(void);   /* thread-local detail of the last failure */
 FFTUP_API const char* fftup_version(void);

@@ -48,6 +48,7 @@ EXPORTS = [
     "fftup_execute_device_views", "fftup_download_view_tables",
     "fftup_align_create", "fftup_align_destroy", "fftup_align_get_info", "fftup_align_shifts",
     "fftup_execute_device_views_shifted", "fftup_shift_path",
+    "fftup_rotate_create", "fftup_rotate_destroy", "fftup_rotate_get_info", "fftup_rotate_frames",
 ]
 ABI_VERSION = 2
 
@@ -99,6 +100,23 @@ class AlignInfo(C.Structure):
 class PathConfig(C.Structure):
     """fftup_path_config"""
     _fields_ = [("mode", C.c_uint32), ("sigma", C.c_float), ("min_peak", C.c_float)]
+
+
+class RotateConfig(C.Structure):
+    """fftup_rotate_config"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("precision", C.c_uint32), ("device", C.c_int32),
+                ("max_batch", C.c_uint32)]
+
+
+class Rotation(C.Structure):
+    """fftup_rotation: content turns by `angle` radians about (centre_x, centre_y), clockwise on screen for a positive angle"""
+    _fields_ = [("angle", C.c_double), ("centre_x", C.c_double), ("centre_y", C.c_double)]
+
+
+class RotateInfo(C.Structure):
+    """fftup_rotate_info"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("num_kernels", C.c_uint32), ("max_batch", C.c_uint32),
+                ("device_bytes", C.c_uint64), ("kernel_names", (C.c_char * 64) * 4)]
 
 
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
@@ -174,5 +192,10 @@ def load():
     lib.fftup_align_shifts.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp, vp]
     lib.fftup_execute_device_views_shifted.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(View), vp, u32, vp]
     lib.fftup_shift_path.argtypes = [C.POINTER(PathConfig), vp, vp, u32, vp]
+    lib.fftup_rotate_create.argtypes = [C.POINTER(vp), C.POINTER(RotateConfig)]
+    lib.fftup_rotate_destroy.argtypes = [vp]
+    lib.fftup_rotate_destroy.restype = None
+    lib.fftup_rotate_get_info.argtypes = [vp, C.POINTER(RotateInfo)]
+    lib.fftup_rotate_frames.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(Rotation), u32, vp]
     _libs[path] = lib
     return lib

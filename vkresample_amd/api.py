@@ -457,6 +457,64 @@ def shift_path(in_ptr, out_ptr, n, mode=PATH_CONSECUTIVE, sigma=0.0, min_peak=0.
     _check(_lib.load().fftup_shift_path(C.byref(cfg), in_ptr, out_ptr, n, s), "fftup_shift_path")
 
 
+class Rotator:
+    """Rotation of frames in device memory by three Fourier shears (fftup_rotate_*, include/fftup.h): every pass is the exact
+    trigonometric interpolant of the frame, on the GPU.  width and height in [2, 4096], 2,3,5,7-smooth; max_batch 0: the library's
+    default.  `.info`: the geometry in effect and the kernel names."""
+
+    def __init__(self, width, height, precision=0, device=0, max_batch=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        cfg = _lib.RotateConfig(width, height, precision, device, max_batch)
+        _check(self._lib.fftup_rotate_create(C.byref(self._h), C.byref(cfg)), "fftup_rotate_create")
+        raw = _lib.RotateInfo()
+        _check(self._lib.fftup_rotate_get_info(self._h, C.byref(raw)), "fftup_rotate_get_info")
+        self.info = {k: int(getattr(raw, k)) for k in ("width", "height", "num_kernels", "max_batch", "device_bytes")}
+        self.info["kernel_names"] = [bytes(n).split(b"\0")[0].decode() for n in raw.kernel_names][:raw.num_kernels]
+        self.width, self.height, self.precision, self.device = width, height, precision, device
+
+    def close(self):
+        if self._h:
+            self._lib.fftup_rotate_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def rotation(self, r):
+        """(angle, cx, cy), or a bare angle about the frame centre ((W - 1) / 2, (H - 1) / 2) -> fftup_rotation"""
+        if isinstance(r, (tuple, list)):
+            angle, cx, cy = r
+            return _lib.Rotation(float(angle), float(cx), float(cy))
+        return _lib.Rotation(float(r), (self.width - 1) / 2.0, (self.height - 1) / 2.0)
+
+    def rotate(self, inputs, outputs, rotations, stream=None):
+        """Frame i: inputs[i] turned by rotations[i] into outputs[i] (DeviceImages of width x height; one image or a sequence per
+        side; outputs[i] may be inputs[i]).  A rotation is (angle, cx, cy) in radians and pixels, or a bare angle about the frame
+        centre.  A list holds one rotation per frame; a single number or one (angle, cx, cy) tuple serves every frame.  Asynchronous:
+        ordered on `stream`, nothing waits here."""
+        ins = [inputs] if isinstance(inputs, DeviceImage) else list(inputs)
+        outs = [outputs] if isinstance(outputs, DeviceImage) else list(outputs)
+        one = np.isscalar(rotations) or (isinstance(rotations, tuple) and len(rotations) == 3 and np.isscalar(rotations[0]))
+        rots = [rotations] * len(ins) if one else list(rotations)
+        if not len(ins) == len(outs) == len(rots):
+            raise ValueError("rotate: %d inputs, %d outputs, %d rotations" % (len(ins), len(outs), len(rots)))
+        a = (_lib.DeviceImageDesc * len(ins))(*[i.desc() for i in ins])
+        b = (_lib.DeviceImageDesc * len(outs))(*[o.desc() for o in outs])
+        c = (_lib.Rotation * len(rots))(*[self.rotation(r) for r in rots])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_rotate_frames(self._h, a, b, c, len(ins), s), "fftup_rotate_frames")
+
+
 class PinnedArray:
     """uint8 numpy view of page-locked host memory from fftup_host_alloc (needed for truly asynchronous copies
     in Upscaler.submit_rgb8); free with .close() after the frames using it have been waited for."""

@@ -31,6 +31,8 @@
 //   -smooth SIGMA [-minpeak P]  with -stabilise: follow a smoothed camera path instead of locking on frame 000001 -- the shifts are
 //                 estimated between consecutive frames, fftup_shift_path (Gaussian of SIGMA frames; frames with a peak below P hold
 //                 the path) turns them into view offsets on the GPU, and the frame lines gain ` offset ox oy`
+//   -rotate DEG [-rotatecentre X,Y]  single image mode: fftup_rotate_frames turns the decoded frame in device memory (three Fourier
+//                 shears, 8-bit to 8-bit, in place), fftup_execute_device runs the plan on it; -rotate 0: the path without the flag
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -76,6 +78,9 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     bool stabilise = false;                  // -stabilise: batched mode, every frame shown where frame 000001 shows the view
     bool smooth = false;                     // -smooth SIGMA: ... where a smoothed camera path shows it (fftup_shift_path)
     float smoothSigma = 0.f, minPeak = 0.f;  // -minpeak P
+    double rotateDeg = 0.0;                  // -rotate DEG: single image mode, the frame is turned in device memory first (0: not at all)
+    bool hasRotateCentre = false;            // -rotatecentre X,Y (default: the frame centre)
+    double rotateCx = 0.0, rotateCy = 0.0;
 };
 
 // frame k of the K views of a move from a to b, t = k / (K - 1): per axis the origin linear in t, the span geometric; the ends exact
@@ -91,6 +96,35 @@ static fftup_view view_between(const fftup_view& a, const fftup_view& b, uint32_
     v.span_x = a.span_x * std::pow(b.span_x / a.span_x, t);
     v.span_y = a.span_y * std::pow(b.span_y / a.span_y, t);
     return v;
+}
+
+// -rotate: the decoded frame goes to device memory, is turned there in place (fftup_rotate_frames, 8-bit to 8-bit) and runs through the
+// plan by fftup_execute_device on the same stream; one blocking copy brings the result back
+static int run_rotated(const ResampleConfiguration& config, fftup_plan* plan, const std::vector<uint8_t>& rgb, int width, int height, uint32_t uW, uint32_t uH,
+                       std::vector<uint8_t>& result)
+{
+    const size_t inBytes = (size_t)width * height * 3, outBytes = (size_t)uW * uH * 3;
+    fftup_rotate_config rc{};
+    rc.width = (uint32_t)width; rc.height = (uint32_t)height; rc.precision = config.precision; rc.device = config.device_id; rc.max_batch = 1;
+    fftup_rotate* rot = nullptr;
+    int res = fftup_rotate_create(&rot, &rc);
+    void* din = res == FFTUP_OK ? fftup_device_alloc(config.device_id, inBytes) : nullptr;
+    void* dout = res == FFTUP_OK ? fftup_device_alloc(config.device_id, outBytes) : nullptr;
+    if (res == FFTUP_OK && !(din && dout)) res = FFTUP_E_OUT_OF_MEMORY;
+    if (res == FFTUP_OK) res = fftup_device_copy(din, rgb.data(), inBytes, 0, nullptr);
+    const fftup_device_image in = {din, FFTUP_FMT_RGB8, (size_t)width * 3, 0}, out = {dout, FFTUP_FMT_RGB8, (size_t)uW * 3, 0};
+    fftup_rotation r;
+    r.angle = config.rotateDeg * 3.14159265358979323846 / 180.0;
+    r.centre_x = config.hasRotateCentre ? config.rotateCx : 0.5 * (width - 1);
+    r.centre_y = config.hasRotateCentre ? config.rotateCy : 0.5 * (height - 1);
+    if (res == FFTUP_OK) res = fftup_rotate_frames(rot, &in, &in, &r, 1, nullptr);
+    if (res == FFTUP_OK) res = fftup_execute_device(plan, &in, &out, 1, nullptr);
+    result.resize(outBytes);
+    if (res == FFTUP_OK) res = fftup_device_copy(result.data(), dout, outBytes, 1, nullptr);    // (ordered behind both, blocking)
+    fftup_rotate_destroy(rot);
+    fftup_device_free(din);
+    fftup_device_free(dout);
+    return res;
 }
 
 // -viewto: ONE image, K views, K files -- the whole clip is one fftup_execute_device_views call on device buffers (the image once,
@@ -471,6 +505,21 @@ static int launchResample(ResampleConfiguration config)                      // 
                 return FFTUP_E_INCOMPLETE;
             }
         }
+        if (config.rotateDeg != 0.0) {                                        // -rotate: single image mode only (main checks)
+            res = run_rotated(config, plan, png_input, width, height, uW, uH, png_output);
+            if (res != FFTUP_OK) printf("Rotated upscale failed: %s (%s)\n", fftup_strerror(res), fftup_last_error());
+            else {
+                printf("VkResample rotated by %g degrees: %dx%d to %dx%d\n", config.rotateDeg, width, height, uW, uH);
+                char rotName[1024];
+                if (config.png_output_name) snprintf(rotName, sizeof rotName, "%s", config.png_output_name);
+                else snprintf(rotName, sizeof rotName, "%d_%d_upscaled.png", width, (int)uW);
+                if (!pngio::write_rgb8(rotName, png_output.data(), (int)uW, (int)uH, (size_t)uW * 3, err))
+                    printf("Could not write %s: %s\n", rotName, err.c_str());
+                printf("Thread %d finished. Device name: %s API:HIP\n", config.threadId, info.device_name);
+            }
+            fftup_plan_destroy(plan);
+            return res;
+        }
         res = fftup_upload_rgb8(plan, png_input.data(), (size_t)width * 3);   // pack loop + transferDataFromCPU
         double totTime = 0;
         if (res == FFTUP_OK) res = fftup_execute(plan, config.numIter, &totTime);   // performVulkanUpscale, VR:1692
@@ -550,6 +599,7 @@ int main(int argc, char* argv[])
         printf("	-viewto OX,OY,SX,SY -frames K: with -size and -view, single image mode: a clip of K frames (2 to 9999) whose view moves from -view to -viewto (position linear, span geometric); -o NAME.png gives NAME_0001.png ...; the views are printed, one 'view k: ox oy sx sy' line each\n");
         printf("	-stabilise: batched mode with -size [-view] [-mirror]: frame 000001 is the reference; every frame's shift against it is estimated on the GPU (phase correlation) and the frame is shown at the view moved by that shift; one 'frame N: shift dx dy peak p' line each; one thread, one device\n");
         printf("	-smooth SIGMA [-minpeak P]: with -stabilise: follow a smoothed camera path instead of locking on frame 000001: shifts between consecutive frames, accumulated and low-passed on the GPU by a Gaussian of SIGMA frames (0 to 256; 0 locks on frame 000001); frames whose peak is below P hold the path; the frame lines gain ' offset ox oy'; at most 4096 frames\n");
+        printf("	-rotate DEG [-rotatecentre X,Y]: single image mode: turn the image by DEG degrees (-90 to 90, clockwise on screen) about its centre or about pixel position (X, Y) before it is resampled: three Fourier shears in device memory, exact trigonometric interpolation; the image is periodic, so corners that leave the frame come back at the opposite border; width and height up to 4096 with factors 2, 3, 5, 7 (-p 0 and -p 2)\n");
         return 0;
     }
     if (findFlag(B, E, "-devices")) return devices_list();
@@ -661,6 +711,26 @@ int main(int argc, char* argv[])
             printf("No proper peak is selected with -minpeak flag (a number, e.g. 0.1)\n");
             return 1;
         }
+    }
+    if (findFlag(B, E, "-rotate")) {
+        char* v = getFlagValue(B, E, "-rotate");
+        char tail = 0;
+        if (!v || sscanf(v, "%lf%c", &config.rotateDeg, &tail) != 1 || !(config.rotateDeg >= -90.0 && config.rotateDeg <= 90.0)) {
+            printf("No proper angle is selected with -rotate flag (degrees, a number from -90 to 90)\n");
+            return 1;
+        }
+        if (findFlag(B, E, "-ifolder") || config.frames) { printf("-rotate works on one image (-i): it cannot be combined with -ifolder or -viewto\n"); return 1; }
+        if (config.precision == 1) { printf("-rotate turns 8-bit frames and float or half planes: it cannot be combined with -p 1\n"); return 1; }
+    }
+    if (findFlag(B, E, "-rotatecentre")) {
+        char* v = getFlagValue(B, E, "-rotatecentre");
+        char tail = 0;
+        if (!findFlag(B, E, "-rotate")) { printf("-rotatecentre names the centre of -rotate: it cannot be used without it\n"); return 1; }
+        if (!v || sscanf(v, "%lf,%lf%c", &config.rotateCx, &config.rotateCy, &tail) != 2 || !std::isfinite(config.rotateCx) || !std::isfinite(config.rotateCy)) {
+            printf("No proper centre is selected with -rotatecentre flag (X,Y, e.g. 959.5,539.5)\n");
+            return 1;
+        }
+        config.hasRotateCentre = true;
     }
     if (config.stabilise) {
         // what the mode cannot serve: one line, exit code 1

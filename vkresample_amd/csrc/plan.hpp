@@ -10,6 +10,7 @@
 //   fftup_png.hip      the device-side PNG encoder's host side
 //   fftup_device_io.hip  frames in caller-owned device memory: fftup_execute_device, fftup_execute_device_views[_shifted] and the device / stream helpers
 //   fftup_align.hip    shift estimates: the aligner object (fftup_align_*), beside the plan, and the launches of kernels_align.hpp; fftup_shift_path
+//   fftup_rotate.hip   rotation by three shears: the rotator object (fftup_rotate_*), beside the plan, and the launches of kernels_rotate.hpp
 //   jit.cpp            the plan-time compiler
 //   jit_choose.cpp     the plan-time chooser: which factorizations a specialised plan runs (no device)
 #pragma once

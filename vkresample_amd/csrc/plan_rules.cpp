@@ -678,3 +678,32 @@ int align_geometry(const fftup_align_config& c, AlignGeometry& G)
     G.Ky = G.band_ky < G.ny / 2 ? 2 * G.band_ky + 1 : G.ny;
     return FFTUP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ rotate_geometry
+// fftup_rotate_create: the rules and decisions of a rotator (include/fftup.h), arithmetic on the configuration alone.
+// The longest line: both shear kernels hold two LDS buffers of two interleaved sequences at that length (rows: R + i G and B + i 0
+// side by side; columns: a tile of at least two), 2 * 2 * lpad(4096) * 8 B = 139 280 B of the 160 KB of a gfx950 compute unit.  A
+// line of 8192 points would need 278 KB.
+static constexpr uint32_t ROTATE_MAX_N = 4096;
+
+int rotate_geometry(const fftup_rotate_config& c, RotateGeometry& G)
+{
+    const char* who = "fftup_rotate_create: ";
+    if (c.precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes): there are no -p 1 frames");
+    if (c.precision > 2) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes)");
+    const uint32_t len[2] = {c.width, c.height};
+    for (int a = 0; a < 2; a++) {
+        const std::string at = std::string(who) + (a ? "height " : "width ") + std::to_string(len[a]);
+        if (len[a] < 2) return fail(FFTUP_E_UNSUPPORTED_SIZE, at + " is below 2");
+        if (len[a] > ROTATE_MAX_N) return fail(FFTUP_E_UNSUPPORTED_SIZE, at + " is above " + std::to_string(ROTATE_MAX_N) + " (two LDS buffers of two sequences)");
+        if (!is_smooth(len[a])) return fail(FFTUP_E_UNSUPPORTED_SIZE, at + " has a prime factor above 7 (a rotator has no Bluestein path)");
+    }
+    if (c.max_batch > 64) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "max_batch " + std::to_string(c.max_batch) + " must be <= 64 (0: 4)");
+    G.W = c.width; G.H = c.height; G.precision = c.precision;
+    G.max_batch = c.max_batch ? c.max_batch : 4;
+    G.TK = 2 * c.height <= ROTATE_MAX_N ? 4 : 2;            // the widest tile of 4, 2 whose two buffers fit
+    G.lds_x = 2 * sizeof(float2) * (size_t)lpad_size(2 * (int)G.W);
+    G.lds_y = 2 * sizeof(float2) * (size_t)lpad_size((int)(G.TK * G.H));
+    if (G.lds_x > LDS_GFX950 || G.lds_y > LDS_GFX950) return fail(FFTUP_E_UNSUPPORTED_SIZE, std::string(who) + "the transforms do not fit the LDS");
+    return FFTUP_OK;
+}

@@ -133,4 +133,12 @@ struct AlignGeometry {
     float band = 0.5f;
 };
 int align_geometry(const fftup_align_config& c, AlignGeometry& G);
+
+// ---- fftup_rotate_create: every rule and decision of a rotator (include/fftup.h, "rotation by three shears"), before any device
+// access.  TK: adjacent columns per workgroup of the column pass; lds_x / lds_y: dynamic LDS of the row / column kernels in bytes
+struct RotateGeometry {
+    uint32_t W = 0, H = 0, precision = 0, max_batch = 4, TK = 4;
+    size_t lds_x = 0, lds_y = 0;
+};
+int rotate_geometry(const fftup_rotate_config& c, RotateGeometry& G);
 float const_via_percent_f(double v, bool half);
