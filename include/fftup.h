@@ -695,6 +695,94 @@ FFTUP_API int fftup_rotate_get_info(const fftup_rotate* r, fftup_rotate_info* in
 FFTUP_API int fftup_rotate_frames(fftup_rotate* r, const fftup_device_image* in, const fftup_device_image* out,
                                   const fftup_rotation* rotations, uint32_t n_frames, void* stream /* hipStream_t; NULL = the default stream */);
 
+/* EXTENSION: roll estimates -- what the rotator needs to undo camera roll.  A ROLL ESTIMATOR is a small object beside the plan, like
+ * the aligner: for pairs of frames in device memory, fftup_roll_angles estimates the rotation between ref[i] and cur[i] about the
+ * optical axis, entirely on the GPU, from the magnitudes of their spectra alone: a translation between the frames changes only the
+ * phases and does not enter.  angle is in radians with the rotator's sign, cur ~ fftup_rotate_frames(ref, +angle): rotating cur by
+ * -angle (fftup_rotate_frames_angles with gain = -1) undoes the roll.  The magnitude of a real frame's spectrum is symmetric about
+ * the origin, so a roll is measured modulo pi: the answer lies in [-pi/2, pi/2).
+ * Detect the feature by these symbols; fftup_version() and FFTUP_ABI_VERSION are unchanged.
+ *
+ * Geometry (arithmetic on the configuration, decided before any device access; fftup_last_error names the rule;
+ * fftup_roll_get_info reports it).  Box mean, crop and window as for the aligner, with windows of at most 512: the transform is
+ * zero-padded to 2 n_x x 2 n_y and 1024 is the longest line of the aligner's LDS transforms.  decimate = 0: the smallest d of 1, 2,
+ * 4, 8 for which the largest powers of two <= W / d and <= H / d are both <= 512 (none: 8, the window capped at 512); window = 0:
+ * those powers of two.  n = min(n_x, n_y); angles = 0: n_theta = n; rho_max = floor(band n) and rho_min = max(2, rho_max / 4)
+ * (integer division), radii in bins of the padded transform; m_b = n_theta / 4; K = 2 m_b.
+ * FFTUP_E_INVALID_ARG: a window that is not a power of two in [32, 512] or with window * d above the frame, d not 1, 2, 4 or 8, a
+ * frame below 32 decimated pixels on an axis, band outside (0, 1] or with rho_max < 2, angles not a power of two in [32, 1024],
+ * upsample outside [4, 64]; FFTUP_E_UNSUPPORTED_PRECISION: precision 1.
+ *
+ * The estimate, per pair (fp32 arithmetic, the sums of step 6 in fp64; tests/roll_oracle.py restates it in fp64):
+ *   1. Step 1 of the aligner: luma, d x d box mean, centred crop, the separable half-sample Hann window: a (ref) and b (cur).
+ *   2. a + i b in the top-left n_y x n_x corner of a zero array of 2 n_y x 2 n_x; ONE complex transform Z, unnormalised;
+ *      A[k] = (Z[k] + conj Z[-k]) / 2, B[k] = (Z[k] - conj Z[-k]) / 2i.  Only rows 0 <= k_y <= rho_max n_y / n + 1 and columns
+ *      |k_x| <= rho_max n_x / n + 1 are computed: nothing else is read.  (Without the padding the bilinear samples of step 3 carry
+ *      a pattern fixed to the grid, which phase-only weighting amplifies: small angles lock onto 0.)
+ *   3. M_A = log1p |A|, M_B = log1p |B|.  theta_j = pi j / n_theta, j < n_theta; for rho = rho_min .. rho_max the sample at
+ *      k_x = rho cos(theta_j) n_x / n, k_y = rho sin(theta_j) n_y / n, bilinear between the four bins around it, indices modulo the
+ *      padded lengths: profiles L_A[rho][j], L_B[rho][j].
+ *   4. F_rho = DFT_{n_theta}(L[rho][.]); P[m] = sum_rho F^B_rho[m] conj F^A_rho[m]; R[m] = P[m] / |P[m]| for 1 <= |m| <= m_b where
+ *      |P[m]| > 1e-9 max |P| over that band; R = 0 elsewhere (m = 0 too, and everywhere when the maximum is 0).
+ *   5. r = Re IDFT(R) on the n_theta grid; coarse peak p = argmax (lowest index on a tie), peak_coarse = r_max n_theta / K
+ *      (identical frames: 1).
+ *   6. r(u) = (1 / n_theta) Re sum_m R[m] exp(2 pi i m u / n_theta) on the 2 kappa + 1 points u = p + i / kappa, |i| <= kappa;
+ *      argmax (same tie rule); the vertex delta of the parabola through the maximum and its two fine neighbours (0 on the grid's
+ *      edge or for a zero denominator); peak = the fine maximum times n_theta / K.
+ *   7. s = p + (i + delta) / kappa, wrapped to [-n_theta / 2, n_theta / 2); angle = pi s / n_theta.  A pair of black frames:
+ *      R = 0, and steps 5-7 give angle = -pi / n_theta, peak = peak_coarse = 0 by the tie rule alone.
+ * Window size: a roll moves the spectrum by an angle, and the angular resolution of a window of n pixels is about 1 / n radians
+ * before the fit: 128 x 128 recovers a roll within about a milliradian, 512 x 256 within half of that, 64 x 32 is a legal geometry but
+ * errs by up to 20 mrad.  DESIGN.md has the figures.
+ *
+ * Ordering and containment, as fftup_align_shifts: everything is enqueued on `stream`, the host is never synchronised, the
+ * descriptor arrays are read before the call returns; the frames are only read; exactly n_pairs * sizeof(fftup_roll_angle) bytes of
+ * angles_device are written (reserved = 0).  The buffers of max_batch pairs are allocated at creation, fftup_roll_angles allocates
+ * nothing; a longer call runs in chunks, in stream order.  No atomics: the same call gives the same bytes.  One host thread per
+ * estimator at a time.
+ * Validation happens before any launch: FFTUP_E_INVALID_ARG for null pointers, n_pairs == 0 and every descriptor rule of
+ * fftup_execute_device (format, strides, device memory of the estimator's device -- angles_device too, which must be a multiple of 4). */
+typedef struct fftup_roll_config {
+    uint32_t width, height;      /* the frames' size */
+    uint32_t precision;          /* element type of FFTUP_FMT_PLANAR frames: 0 float, 2 IEEE half (1: FFTUP_E_UNSUPPORTED_PRECISION) */
+    int32_t  device;
+    uint32_t window_w, window_h; /* window in decimated pixels: powers of two in [32, 512]; 0 = automatic */
+    uint32_t decimate;           /* d: box-average d x d input pixels first; 1, 2, 4 or 8; 0 = automatic */
+    float    band;               /* rho_max = floor(band * n), (0, 1]; 0 = 0.5 */
+    uint32_t angles;             /* n_theta: angular samples over [0, pi), a power of two in [32, 1024]; 0 = min(window_w, window_h) */
+    uint32_t upsample;           /* kappa: fine-grid points per angular sample, 4..64; 0 = 32 */
+    uint32_t max_batch;          /* pairs whose buffers are held; 0 = 16; longer calls run in chunks */
+} fftup_roll_config;
+typedef struct fftup_roll_angle { float angle, peak, peak_coarse, reserved; } fftup_roll_angle;
+typedef struct fftup_roll fftup_roll;
+typedef struct fftup_roll_info {
+    uint32_t window_w, window_h, decimate, crop_x, crop_y, upsample, n, angles, rho_min, rho_max, m_band, K, max_batch, num_kernels;
+    uint64_t device_bytes;
+    char     kernel_names[8][64];
+} fftup_roll_info;
+FFTUP_API int fftup_roll_create(fftup_roll** out, const fftup_roll_config* cfg);
+FFTUP_API void fftup_roll_destroy(fftup_roll* r);
+FFTUP_API int fftup_roll_get_info(const fftup_roll* r, fftup_roll_info* info);
+FFTUP_API int fftup_roll_angles(fftup_roll* r, const fftup_device_image* ref, const fftup_device_image* cur,
+                                uint32_t n_pairs, fftup_roll_angle* angles_device, void* stream /* hipStream_t; NULL = the default stream */);
+
+/* EXTENSION: the rotator reads its angles on the GPU -- the estimates above reach the rotator without a host copy.
+ * fftup_rotate_frames_angles is fftup_rotate_frames with ONE change: frame i is turned by
+ *     theta_i = rotations[i].angle + gain * (double)angles_device[i].angle
+ * about rotations[i]'s centre.  gain = -1 undoes a measured roll.  theta_i is formed on the device, by one small kernel per chunk
+ * (rotate_coeffs) that writes the shear coefficients a = -tan(theta_i / 2), b = sin(theta_i) in double to a buffer made at
+ * creation; the three shear kernels read them there.  The host never reads angles_device and never waits for it, so the output of
+ * fftup_roll_angles enqueued on `stream` before this call is consumed without a synchronisation.  A device angle that is not finite
+ * counts as 0; theta_i is clamped to [-pi/2, pi/2] (the host cannot refuse what it never reads); peak and peak_coarse are not read.
+ * The result is fftup_rotate_frames' at theta_i up to the last place of tan and sin in double, which may differ between the device
+ * and the host's libm.  Exactly n_frames * sizeof(fftup_roll_angle) bytes are read at angles_device, nothing is written there.
+ * FFTUP_E_INVALID_ARG, before anything is enqueued: everything fftup_rotate_frames refuses (|rotations[i].angle| > pi/2 included);
+ * angles_device null, not a multiple of 4, or not device memory of the rotator's device; a gain that is not finite.
+ * Detect the feature by this symbol; fftup_rotate_frames, fftup_version() and FFTUP_ABI_VERSION are unchanged. */
+FFTUP_API int fftup_rotate_frames_angles(fftup_rotate* r, const fftup_device_image* in, const fftup_device_image* out,
+                                         const fftup_rotation* rotations, const fftup_roll_angle* angles_device, double gain,
+                                         uint32_t n_frames, void* stream);
+
 FFTUP_API const char* fftup_strerror(int code);
 FFTUP_API const char* fftup_last_error(void);   /* thread-local detail of the last failure */
 FFTUP_API const char* fftup_version(void);

@@ -96,11 +96,11 @@ int main(int argc, char** argv)
     std::vector<float> t[3];
     for (int r = 0; r <= rounds; r++) {                      // (round 0 warms up)
         CHECK(hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(k_rotate_shear_x<0>, dim3(H, 1, frames), dim3(thrX), lds_x, st, p, q, 0);
+        hipLaunchKernelGGL(k_rotate_shear_x<0>, dim3(H, 1, frames), dim3(thrX), lds_x, st, p, q, 0, (const double2*)nullptr);
         CHECK(hipEventRecord(ev[1], st));
-        hipLaunchKernelGGL(shear_y, dim3((W + TK - 1) / TK, 2, frames), dim3(thrY), lds_y, st, p, q, 0);
+        hipLaunchKernelGGL(shear_y, dim3((W + TK - 1) / TK, 2, frames), dim3(thrY), lds_y, st, p, q, 0, (const double2*)nullptr);
         CHECK(hipEventRecord(ev[2], st));
-        hipLaunchKernelGGL(k_rotate_shear_x<1>, dim3(H, 1, frames), dim3(thrX), lds_x, st, p, q, 0);
+        hipLaunchKernelGGL(k_rotate_shear_x<1>, dim3(H, 1, frames), dim3(thrX), lds_x, st, p, q, 0, (const double2*)nullptr);
         CHECK(hipEventRecord(ev[3], st));
         CHECK(hipGetLastError());
         CHECK(hipEventSynchronize(ev[3]));

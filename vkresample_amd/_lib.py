@@ -49,6 +49,7 @@ EXPORTS = [
     "fftup_align_create", "fftup_align_destroy", "fftup_align_get_info", "fftup_align_shifts",
     "fftup_execute_device_views_shifted", "fftup_shift_path",
     "fftup_rotate_create", "fftup_rotate_destroy", "fftup_rotate_get_info", "fftup_rotate_frames",
+    "fftup_roll_create", "fftup_roll_destroy", "fftup_roll_get_info", "fftup_roll_angles", "fftup_rotate_frames_angles",
 ]
 ABI_VERSION = 2
 
@@ -117,6 +118,25 @@ class RotateInfo(C.Structure):
     """fftup_rotate_info"""
     _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("num_kernels", C.c_uint32), ("max_batch", C.c_uint32),
                 ("device_bytes", C.c_uint64), ("kernel_names", (C.c_char * 64) * 4)]
+
+
+class RollConfig(C.Structure):
+    """fftup_roll_config"""
+    _fields_ = [("width", C.c_uint32), ("height", C.c_uint32), ("precision", C.c_uint32), ("device", C.c_int32),
+                ("window_w", C.c_uint32), ("window_h", C.c_uint32), ("decimate", C.c_uint32), ("band", C.c_float),
+                ("angles", C.c_uint32), ("upsample", C.c_uint32), ("max_batch", C.c_uint32)]
+
+
+class RollAngle(C.Structure):
+    """fftup_roll_angle: cur ~ ref turned by `angle` radians, the rotator's sign"""
+    _fields_ = [("angle", C.c_float), ("peak", C.c_float), ("peak_coarse", C.c_float), ("reserved", C.c_float)]
+
+
+class RollInfo(C.Structure):
+    """fftup_roll_info"""
+    _fields_ = [(k, C.c_uint32) for k in ("window_w", "window_h", "decimate", "crop_x", "crop_y", "upsample", "n", "angles", "rho_min",
+                                          "rho_max", "m_band", "K", "max_batch", "num_kernels")] + \
+               [("device_bytes", C.c_uint64), ("kernel_names", (C.c_char * 64) * 8)]
 
 
 KNOBS_LIB_PATH = os.path.join(HERE, "libfftup_knobs.so")       # the same objects + the FFTUP_EXPERIMENT parser (tests, tools)
@@ -197,5 +217,11 @@ def load():
     lib.fftup_rotate_destroy.restype = None
     lib.fftup_rotate_get_info.argtypes = [vp, C.POINTER(RotateInfo)]
     lib.fftup_rotate_frames.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(Rotation), u32, vp]
+    lib.fftup_roll_create.argtypes = [C.POINTER(vp), C.POINTER(RollConfig)]
+    lib.fftup_roll_destroy.argtypes = [vp]
+    lib.fftup_roll_destroy.restype = None
+    lib.fftup_roll_get_info.argtypes = [vp, C.POINTER(RollInfo)]
+    lib.fftup_roll_angles.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), u32, vp, vp]
+    lib.fftup_rotate_frames_angles.argtypes = [vp, C.POINTER(DeviceImageDesc), C.POINTER(DeviceImageDesc), C.POINTER(Rotation), vp, C.c_double, u32, vp]
     _libs[path] = lib
     return lib

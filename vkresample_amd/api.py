@@ -514,6 +514,78 @@ class Rotator:
         s = stream.handle if isinstance(stream, Stream) else stream
         _check(self._lib.fftup_rotate_frames(self._h, a, b, c, len(ins), s), "fftup_rotate_frames")
 
+    def frames_angles(self, inputs, outputs, rotations, angles_ptr, gain=-1.0, stream=None):
+        """rotate() with frame i turned by rotations[i]'s angle + gain * the angle of the fftup_roll_angle at angles_ptr + 16 i, device
+        memory -- what Roller.angles_device wrote there; the sum is formed on the GPU, the host never reads the angles.  gain = -1
+        undoes a measured roll.  Asynchronous: ordered on `stream`, nothing waits here."""
+        ins = [inputs] if isinstance(inputs, DeviceImage) else list(inputs)
+        outs = [outputs] if isinstance(outputs, DeviceImage) else list(outputs)
+        one = np.isscalar(rotations) or (isinstance(rotations, tuple) and len(rotations) == 3 and np.isscalar(rotations[0]))
+        rots = [rotations] * len(ins) if one else list(rotations)
+        if not len(ins) == len(outs) == len(rots):
+            raise ValueError("frames_angles: %d inputs, %d outputs, %d rotations" % (len(ins), len(outs), len(rots)))
+        a = (_lib.DeviceImageDesc * len(ins))(*[i.desc() for i in ins])
+        b = (_lib.DeviceImageDesc * len(outs))(*[o.desc() for o in outs])
+        c = (_lib.Rotation * len(rots))(*[self.rotation(r) for r in rots])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_rotate_frames_angles(self._h, a, b, c, angles_ptr, float(gain), len(ins), s), "fftup_rotate_frames_angles")
+
+
+class Roller:
+    """Roll estimates between pairs of frames in device memory (fftup_roll_*, include/fftup.h): the rotation about the optical axis
+    from the spectra's magnitudes on a polar grid, phase-only correlation along the angle with a sub-sample refinement, on the GPU.
+    `window`: (window_w, window_h) in decimated pixels or None (automatic); the zeros of the other arguments are the library's
+    defaults.  `.info`: the geometry in effect and the kernel names."""
+
+    def __init__(self, width, height, precision=0, device=0, window=None, decimate=0, band=0.0, angles=0, upsample=0, max_batch=0):
+        self._lib = _lib.load()
+        self._h = C.c_void_p()
+        w = window or (0, 0)
+        cfg = _lib.RollConfig(width, height, precision, device, w[0], w[1], decimate, band, angles, upsample, max_batch)
+        _check(self._lib.fftup_roll_create(C.byref(self._h), C.byref(cfg)), "fftup_roll_create")
+        raw = _lib.RollInfo()
+        _check(self._lib.fftup_roll_get_info(self._h, C.byref(raw)), "fftup_roll_get_info")
+        self.info = {k: int(getattr(raw, k)) for k, _ in _lib.RollInfo._fields_ if k != "kernel_names"}
+        self.info["kernel_names"] = [bytes(n).split(b"\0")[0].decode() for n in raw.kernel_names][:raw.num_kernels]
+        self.width, self.height, self.precision, self.device = width, height, precision, device
+
+    def close(self):
+        if self._h:
+            self._lib.fftup_roll_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def angles_device(self, refs, curs, out_ptr, stream=None):
+        """Pair i = (refs[i], curs[i]), DeviceImages of width x height (one image or a sequence per side; a single ref is repeated for
+        every cur): its fftup_roll_angle goes to out_ptr + 16 i, device memory.  Asynchronous: ordered on `stream`, nothing waits here."""
+        cs = [curs] if isinstance(curs, DeviceImage) else list(curs)
+        rs = [refs] * len(cs) if isinstance(refs, DeviceImage) else list(refs)
+        if len(rs) != len(cs):
+            raise ValueError("angles_device: %d reference frames, %d current frames" % (len(rs), len(cs)))
+        a = (_lib.DeviceImageDesc * len(rs))(*[r.desc() for r in rs])
+        b = (_lib.DeviceImageDesc * len(cs))(*[c.desc() for c in cs])
+        s = stream.handle if isinstance(stream, Stream) else stream
+        _check(self._lib.fftup_roll_angles(self._h, a, b, len(cs), out_ptr, s), "fftup_roll_angles")
+
+    def angles(self, refs, curs, stream=None):
+        """-> (n, 4) float32: angle, peak, peak_coarse, 0 per pair, cur ~ ref turned by +angle radians.  Blocking: allocates the
+        result buffer, runs angles_device and copies back on `stream`."""
+        n = 1 if isinstance(curs, DeviceImage) else len(curs)
+        with DeviceBuffer(max(1, n) * 16, self.device) as buf:
+            self.angles_device(refs, curs, buf.ptr, stream)
+            return buf.download(stream=stream).view(np.float32).reshape(n, 4).copy()
+
 
 class PinnedArray:
     """uint8 numpy view of page-locked host memory from fftup_host_alloc (needed for truly asynchronous copies

@@ -28,6 +28,8 @@
 //                 fftup_execute_device_views call on device buffers; K files, -o NAME.png -> NAME_0001.png ...
 //   -stabilise    batched mode with -size [-view] [-mirror]: fftup_align_shifts estimates every frame's shift against frame 000001,
 //                 fftup_execute_device_views_shifted shows each frame at the view moved by its shift, read from device memory
+//   -roll         with -stabilise: fftup_roll_angles estimates every frame's roll against frame 000001, fftup_rotate_frames_angles turns
+//                 the frame back by it (gain -1, the angle read in device memory), then shifts and views work on the level frames
 //   -smooth SIGMA [-minpeak P]  with -stabilise: follow a smoothed camera path instead of locking on frame 000001 -- the shifts are
 //                 estimated between consecutive frames, fftup_shift_path (Gaussian of SIGMA frames; frames with a peak below P hold
 //                 the path) turns them into view offsets on the GPU, and the frame lines gain ` offset ox oy`
@@ -75,6 +77,7 @@ struct ResampleConfiguration {           // VkResampleConfiguration, VR:45-59
     fftup_view view{};
     uint32_t frames = 0;                     // -viewto ox,oy,sx,sy -frames K: a clip of K views from `view` to `viewTo` (0: none)
     fftup_view viewTo{};
+    bool roll = false;                       // -roll with -stabilise: every frame's roll against frame 000001 is estimated and undone first
     bool stabilise = false;                  // -stabilise: batched mode, every frame shown where frame 000001 shows the view
     bool smooth = false;                     // -smooth SIGMA: ... where a smoothed camera path shows it (fftup_shift_path)
     float smoothSigma = 0.f, minPeak = 0.f;  // -minpeak P
@@ -206,26 +209,52 @@ static int run_stabilise(const ResampleConfiguration& config)
     cfg.precision = config.precision; cfg.sharpen = config.sharpenConst; cfg.device = config.device_id; cfg.flags = config.flags; cfg.ring = 1;
     fftup_align_config acfg{};
     acfg.width = (uint32_t)width; acfg.height = (uint32_t)height; acfg.device = config.device_id;
+    fftup_roll_config rcfg{};
+    rcfg.width = (uint32_t)width; rcfg.height = (uint32_t)height; rcfg.device = config.device_id;
+    fftup_rotate_config tcfg{};
+    tcfg.width = (uint32_t)width; tcfg.height = (uint32_t)height; tcfg.device = config.device_id;
     fftup_plan* plan = nullptr;
     fftup_align* aligner = nullptr;
+    fftup_roll* roller = nullptr;
+    fftup_rotate* rotator = nullptr;
     int res = fftup_plan_create_view(&plan, &cfg, uW, uH, &view);
     if (res == FFTUP_OK) res = fftup_align_create(&aligner, &acfg);
+    if (res == FFTUP_OK && config.roll) res = fftup_roll_create(&roller, &rcfg);
+    if (res == FFTUP_OK && config.roll) res = fftup_rotate_create(&rotator, &tcfg);
     void* din = res == FFTUP_OK ? fftup_device_alloc(config.device_id, inBytes * N) : nullptr;
     void* dout = res == FFTUP_OK ? fftup_device_alloc(config.device_id, outBytes * N) : nullptr;
     void* dshift = res == FFTUP_OK ? fftup_device_alloc(config.device_id, sizeof(fftup_shift) * N) : nullptr;
     void* doffset = res == FFTUP_OK && config.smooth ? fftup_device_alloc(config.device_id, sizeof(fftup_shift) * N) : nullptr;
-    if (res == FFTUP_OK && !(din && dout && dshift && (doffset || !config.smooth))) res = FFTUP_E_OUT_OF_MEMORY;
+    void* dlevel = res == FFTUP_OK && config.roll ? fftup_device_alloc(config.device_id, inBytes * N) : nullptr;    // the de-rotated frames
+    void* dangle = res == FFTUP_OK && config.roll ? fftup_device_alloc(config.device_id, sizeof(fftup_roll_angle) * N) : nullptr;
+    if (res == FFTUP_OK && !(din && dout && dshift && (doffset || !config.smooth) && ((dlevel && dangle) || !config.roll))) res = FFTUP_E_OUT_OF_MEMORY;
     std::vector<fftup_shift> shifts((size_t)N), offsets((size_t)N);
+    std::vector<fftup_roll_angle> angles((size_t)N);
     std::vector<uint8_t> host(res == FFTUP_OK ? outBytes * N : 0);
     if (res == FFTUP_OK) res = fftup_device_copy(din, frames.data(), inBytes * N, 0, nullptr);
     if (res == FFTUP_OK) {
         std::vector<fftup_device_image> ref((size_t)N), in((size_t)N), out((size_t)N);
+        // -roll: every frame's roll against frame 000001, the frames turned back by it into `dlevel` (the angles read by the GPU);
+        // shifts and the render then work on the level frames
+        uint8_t* base = (uint8_t*)(config.roll ? dlevel : din);
+        if (config.roll) {
+            std::vector<fftup_device_image> first((size_t)N), raw((size_t)N), level((size_t)N);
+            const std::vector<fftup_rotation> about((size_t)N, fftup_rotation{0.0, 0.5 * (width - 1), 0.5 * (height - 1)});
+            for (int f = 0; f < N; f++) {
+                first[f] = {din, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+                raw[f] = {(uint8_t*)din + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+                level[f] = {base + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            }
+            res = fftup_roll_angles(roller, first.data(), raw.data(), (uint32_t)N, (fftup_roll_angle*)dangle, nullptr);
+            if (res == FFTUP_OK)
+                res = fftup_rotate_frames_angles(rotator, raw.data(), level.data(), about.data(), (const fftup_roll_angle*)dangle, -1.0, (uint32_t)N, nullptr);
+        }
         for (int f = 0; f < N; f++) {
-            ref[f] = {(uint8_t*)din + (config.smooth && f ? inBytes * (f - 1) : 0), FFTUP_FMT_RGB8, (size_t)width * 3, 0};
-            in[f] = {(uint8_t*)din + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            ref[f] = {base + (config.smooth && f ? inBytes * (f - 1) : 0), FFTUP_FMT_RGB8, (size_t)width * 3, 0};
+            in[f] = {base + inBytes * f, FFTUP_FMT_RGB8, (size_t)width * 3, 0};
             out[f] = {(uint8_t*)dout + outBytes * f, FFTUP_FMT_RGB8, (size_t)uW * 3, 0};
         }
-        res = fftup_align_shifts(aligner, ref.data(), in.data(), (uint32_t)N, (fftup_shift*)dshift, nullptr);
+        if (res == FFTUP_OK) res = fftup_align_shifts(aligner, ref.data(), in.data(), (uint32_t)N, (fftup_shift*)dshift, nullptr);
         if (res == FFTUP_OK && config.smooth) {
             const fftup_path_config pcfg{FFTUP_PATH_CONSECUTIVE, config.smoothSigma, config.minPeak};
             res = fftup_shift_path(&pcfg, (const fftup_shift*)dshift, (fftup_shift*)doffset, (uint32_t)N, nullptr);
@@ -237,9 +266,11 @@ static int run_stabilise(const ResampleConfiguration& config)
         // (for printing only, behind the render call)
         if (res == FFTUP_OK) res = fftup_device_copy(shifts.data(), dshift, sizeof(fftup_shift) * N, 1, nullptr);
         if (res == FFTUP_OK && config.smooth) res = fftup_device_copy(offsets.data(), doffset, sizeof(fftup_shift) * N, 1, nullptr);
+        if (res == FFTUP_OK && config.roll) res = fftup_device_copy(angles.data(), dangle, sizeof(fftup_roll_angle) * N, 1, nullptr);
         for (int f = 0; f < N && res == FFTUP_OK; f++) {
             printf("frame %06d: shift %.3f %.3f peak %.3f", f + 1, shifts[f].dx, shifts[f].dy, shifts[f].peak);
             if (config.smooth) printf(" offset %.3f %.3f", offsets[f].dx, offsets[f].dy);
+            if (config.roll) printf(" roll %.5f rollpeak %.3f", angles[f].angle, angles[f].peak);
             printf("\n");
         }
     }
@@ -247,6 +278,10 @@ static int run_stabilise(const ResampleConfiguration& config)
     fftup_device_free(dout);
     fftup_device_free(dshift);
     fftup_device_free(doffset);
+    fftup_device_free(dlevel);
+    fftup_device_free(dangle);
+    fftup_roll_destroy(roller);
+    fftup_rotate_destroy(rotator);
     fftup_align_destroy(aligner);
     fftup_plan_destroy(plan);
     if (res != FFTUP_OK) {
@@ -598,6 +633,7 @@ int main(int argc, char* argv[])
         printf("	-mirror: with -size and -view: continue the image by its reflection instead of periodically: no wrap-around at the borders, e.g. -size 1920x1080 -view -0.144,-0.144,1366,768 -mirror -anysize on 1366x768 (-p 0 and -p 2, not with -dct)\n");
         printf("	-viewto OX,OY,SX,SY -frames K: with -size and -view, single image mode: a clip of K frames (2 to 9999) whose view moves from -view to -viewto (position linear, span geometric); -o NAME.png gives NAME_0001.png ...; the views are printed, one 'view k: ox oy sx sy' line each\n");
         printf("	-stabilise: batched mode with -size [-view] [-mirror]: frame 000001 is the reference; every frame's shift against it is estimated on the GPU (phase correlation) and the frame is shown at the view moved by that shift; one 'frame N: shift dx dy peak p' line each; one thread, one device\n");
+        printf("	-roll: with -stabilise: every frame's roll against frame 000001 is estimated on the GPU (spectral magnitudes on a polar grid) and the frame is turned back by it about its centre before its shift is estimated and the view rendered; the angle is read by the rotator in device memory; frame sizes as -rotate (2,3,5,7-smooth, at most 4096), at least 32 pixels per axis; the frame lines gain ' roll r rollpeak p' (radians)\n");
         printf("	-smooth SIGMA [-minpeak P]: with -stabilise: follow a smoothed camera path instead of locking on frame 000001: shifts between consecutive frames, accumulated and low-passed on the GPU by a Gaussian of SIGMA frames (0 to 256; 0 locks on frame 000001); frames whose peak is below P hold the path; the frame lines gain ' offset ox oy'; at most 4096 frames\n");
         printf("	-rotate DEG [-rotatecentre X,Y]: single image mode: turn the image by DEG degrees (-90 to 90, clockwise on screen) about its centre or about pixel position (X, Y) before it is resampled: three Fourier shears in device memory, exact trigonometric interpolation; the image is periodic, so corners that leave the frame come back at the opposite border; width and height up to 4096 with factors 2, 3, 5, 7 (-p 0 and -p 2)\n");
         return 0;
@@ -693,6 +729,8 @@ int main(int argc, char* argv[])
     config.stageTimes = findFlag(B, E, "-stagetimes");
     config.gpuPng = findFlag(B, E, "-gpupng");
     config.stabilise = findFlag(B, E, "-stabilise");
+    config.roll = findFlag(B, E, "-roll");
+    if (config.roll && !config.stabilise) { printf("-roll undoes camera roll under -stabilise: it cannot be used without it\n"); return 1; }
     if (findFlag(B, E, "-smooth")) {
         char* v = getFlagValue(B, E, "-smooth");
         char tail = 0;

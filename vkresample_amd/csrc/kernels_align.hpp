@@ -69,6 +69,20 @@ __device__ __forceinline__ float align_px(const AlignImage& im, long x, long y)
     return align_luma(v[0], v[1], v[2]);
 }
 
+// step 1 of the estimate for window pixel (x, y) of a pair: the d x d sums of both frames' luma times w, the product of the window
+// and 1 / d^2 -- (a, b) of z = a + i b.  Shared with the roll estimator (kernels_roll.hpp)
+__device__ __forceinline__ float2 align_window_px(const AlignImage& R, const AlignImage& C, int crop_x, int crop_y, int d, int x, int y, float w)
+{
+    float sa = 0.0f, sb = 0.0f;
+    for (int j = 0; j < d; j++)
+        for (int i = 0; i < d; i++) {
+            const long X = crop_x + (long)x * d + i, Y = crop_y + (long)y * d + j;
+            sa += align_px(R, X, Y);
+            sb += align_px(C, X, Y);
+        }
+    return make_float2(sa * w, sb * w);
+}
+
 // the better of two candidates: the larger value, the lower index on a tie
 __device__ __forceinline__ void align_better(float& v, int& i, float ov, int oi)
 {
@@ -99,17 +113,7 @@ static __global__ void k_align_rows(AlignParams p, AlignPairs q, int pair0)
     const AlignImage& R = q.ref[pz];
     const AlignImage& C = q.cur[pz];
     const float wy = p.winY[y] / (float)(d * d);
-    for (int x = tid; x < nx; x += T) {
-        float sa = 0.0f, sb = 0.0f;
-        for (int j = 0; j < d; j++)
-            for (int i = 0; i < d; i++) {
-                const long X = p.crop_x + (long)x * d + i, Y = p.crop_y + (long)y * d + j;
-                sa += align_px(R, X, Y);
-                sb += align_px(C, X, Y);
-            }
-        const float w = p.winX[x] * wy;
-        a[lpad(x)] = make_float2(sa * w, sb * w);
-    }
+    for (int x = tid; x < nx; x += T) a[lpad(x)] = align_window_px(R, C, p.crop_x, p.crop_y, d, x, y, p.winX[x] * wy);
     __syncthreads();
     const float2* r = fft_lds<-1, 1>(a, b, p.planX, p.twX, tid, T);
     const long row = (long)(pair0 + pz) * p.ny + y;

@@ -1,7 +1,8 @@
 // kernels_rotate.hpp -- rotation by three shears (include/fftup.h, fftup_rotate_frames): R(theta) = Sx(a) Sy(b) Sx(a) with
 // a = -tan(theta / 2), b = sin(theta).  A shear moves every row (column) by its own sub-pixel amount delta: forward transform in
 // LDS, one complex multiply per bin (rotate_phase.hpp: the phase formed and reduced in double), inverse transform, times 1/n.
-// Three launches per chunk of frames, the frame in blockIdx.z, its descriptors and coefficients in the kernel arguments:
+// Three launches per chunk of frames, the frame in blockIdx.z, its descriptors and coefficients in the kernel arguments (the
+// coefficients in a device buffer that k_rotate_coeffs fills first when the angles come from device memory):
 //   k_rotate_shear_x<0>  one workgroup per row: the caller's frame (any of the five kinds of RotateImage) -> T1
 //   k_rotate_shear_y<TK> one workgroup per tile of TK adjacent columns of ONE of the two sequences (blockIdx.y): T1 -> T2; every
 //                        column has its own delta; the last tile of a width that is no multiple of TK is partial
@@ -103,10 +104,29 @@ __device__ __forceinline__ float2 rotate_factor(int k, int n, double delta)
     return make_float2((float)w.re, (float)w.im);
 }
 
+// fftup_rotate_frames_angles: the shear coefficients of a chunk's frames from angles in device memory.  Frame i < n turns by
+// theta = host.angle[i] + gain * (double)angles[i].angle (a device angle that is not finite counts as 0), clamped to [-pi/2, pi/2];
+// coef[i] = (a, b) = (-tan(theta / 2), sin(theta)), what fftup_rotphase::shear_a / shear_b give the host path.  One workgroup.
+constexpr int ROTATE_MAX_BATCH = 64;             // rotate_geometry's limit on max_batch: a chunk's host angles travel as an argument
+struct RotateHostAngles { double angle[ROTATE_MAX_BATCH]; };
+static __global__ void k_rotate_coeffs(RotateHostAngles host, const float* angles, double gain, int n, double2* coef)
+{
+    const int i = threadIdx.x;
+    if (i >= n) return;
+    const float m = angles[4 * (long)i];         // fftup_roll_angle: 4 floats, the angle first
+    const double dm = isfinite(m) ? (double)m : 0.0;
+    const double turn = gain * dm;
+    double theta = host.angle[i] + turn;
+    const double half_pi = 1.57079632679489661923;
+    theta = fmin(fmax(theta, -half_pi), half_pi);
+    coef[i] = make_double2(-tan(0.5 * theta), sin(theta));
+}
+
 // OUT = 0: the caller's frame q.in -> the first intermediate; OUT = 1: the second intermediate -> the caller's frame q.out.
-// frame0: the launch's first frame within the chunk (the index of its intermediates)
+// frame0: the launch's first frame within the chunk (the index of its intermediates); coef: the chunk's shear coefficients in
+// device memory (k_rotate_coeffs), or null: q.a / q.b
 template <int OUT>
-static __global__ void k_rotate_shear_x(RotateParams p, RotateFrames q, int frame0)
+static __global__ void k_rotate_shear_x(RotateParams p, RotateFrames q, int frame0, const double2* coef)
 {
     extern __shared__ float2 rotate_lds[];
     const int y = blockIdx.x, fz = blockIdx.z, tid = threadIdx.x, T = blockDim.x, W = p.W;
@@ -132,7 +152,8 @@ static __global__ void k_rotate_shear_x(RotateParams p, RotateFrames q, int fram
     __syncthreads();
     float2* f = fft_lds<-1, 2>(a, b, p.planW, p.twW, tid, T);
     float2* o = f == a ? b : a;
-    const double delta = q.a[fz] * ((double)y - q.cy[fz]);
+    const double sa = coef ? coef[frame0 + fz].x : q.a[fz];
+    const double delta = sa * ((double)y - q.cy[fz]);
     for (int k = tid; k < W; k += T) {
         const float2 w = rotate_factor(k, W, delta);
         f[lpad(2 * k)] = cmul(f[lpad(2 * k)], w);
@@ -162,7 +183,7 @@ static __global__ void k_rotate_shear_x(RotateParams p, RotateFrames q, int fram
 // blockIdx.x: the tile of columns [TK blockIdx.x, TK blockIdx.x + TK) -- those at or beyond W are zeros in LDS and are never
 // stored; blockIdx.y: 0 the sequence R + i G, 1 the sequence B + i 0; blockIdx.z: the frame of the chunk
 template <int TK>
-static __global__ void k_rotate_shear_y(RotateParams p, RotateFrames q, int frame0)
+static __global__ void k_rotate_shear_y(RotateParams p, RotateFrames q, int frame0, const double2* coef)
 {
     extern __shared__ float2 rotate_lds[];
     const int fz = blockIdx.z, tid = threadIdx.x, T = blockDim.x, W = p.W, H = p.H;
@@ -184,7 +205,7 @@ static __global__ void k_rotate_shear_y(RotateParams p, RotateFrames q, int fram
     __syncthreads();
     float2* f = fft_lds<-1, TK>(a, b, p.planH, p.twH, tid, T);
     float2* o = f == a ? b : a;
-    const double sb = q.b[fz], cx = q.cx[fz];
+    const double sb = coef ? coef[frame0 + fz].y : q.b[fz], cx = q.cx[fz];
     for (int g = tid; g < TK * H; g += T) {
         const double delta = sb * ((double)(x0 + g % TK) - cx);
         f[lpad(g)] = cmul(f[lpad(g)], rotate_factor(g / TK, H, delta));

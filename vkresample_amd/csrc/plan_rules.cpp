@@ -707,3 +707,64 @@ int rotate_geometry(const fftup_rotate_config& c, RotateGeometry& G)
     if (G.lds_x > LDS_GFX950 || G.lds_y > LDS_GFX950) return fail(FFTUP_E_UNSUPPORTED_SIZE, std::string(who) + "the transforms do not fit the LDS");
     return FFTUP_OK;
 }
+
+// ------------------------------------------------------------------------------------------------ roll_geometry
+// fftup_roll_create: the rules and decisions of a roll estimator (include/fftup.h), arithmetic on the configuration alone.
+// The longest window: the transform is zero-padded to twice the window per axis, and 1024 points is the longest line the
+// aligner's LDS transforms (which the roll kernels reuse) are sized for.
+static constexpr uint32_t ROLL_MAX_WINDOW = 512, ROLL_MIN_WINDOW = 32;
+
+int roll_geometry(const fftup_roll_config& c, RollGeometry& G)
+{
+    const char* who = "fftup_roll_create: ";
+    if (c.width == 0 || c.height == 0) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "width and height must be > 0");
+    if (c.width > (1u << 16) || c.height > (1u << 16)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "width/height above 65536");
+    if (c.precision == 1) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes): there are no -p 1 frames");
+    if (c.precision > 2) return fail(FFTUP_E_UNSUPPORTED_PRECISION, std::string(who) + "precision must be 0 (float planes) or 2 (half planes)");
+    if (c.decimate != 0 && c.decimate != 1 && c.decimate != 2 && c.decimate != 4 && c.decimate != 8)
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "decimate " + std::to_string(c.decimate) + " must be 1, 2, 4 or 8 (0: automatic)");
+    const uint32_t win[2] = {c.window_w, c.window_h};
+    for (int a = 0; a < 2; a++)
+        if (win[a] && (win[a] < ROLL_MIN_WINDOW || win[a] > ROLL_MAX_WINDOW || (win[a] & (win[a] - 1))))
+            return fail(FFTUP_E_INVALID_ARG, std::string(who) + (a ? "window_h " : "window_w ") + std::to_string(win[a]) + " must be a power of two in [32, 512] (0: automatic)");
+    if (!(c.band == 0.0f || (c.band > 0.0f && c.band <= 1.0f))) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "band must lie in (0, 1] (0: 0.5)");
+    if (c.angles && (c.angles < 32 || c.angles > 1024 || (c.angles & (c.angles - 1))))
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "angles " + std::to_string(c.angles) + " must be a power of two in [32, 1024] (0: the smaller window length)");
+    if (c.upsample && (c.upsample < 4 || c.upsample > 64)) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "upsample " + std::to_string(c.upsample) + " must lie in [4, 64] (0: 32)");
+    if (c.max_batch > 65535) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "max_batch must be <= 65535");
+    G.W = c.width; G.H = c.height; G.precision = c.precision;
+    G.band = c.band == 0.0f ? 0.5f : c.band;
+    G.kappa = c.upsample ? c.upsample : 32;
+    G.max_batch = c.max_batch ? c.max_batch : 16;
+    // automatic d: the smallest whose automatic windows are both at most 512; none: 8, the windows capped
+    G.d = c.decimate;
+    if (!G.d) {
+        G.d = 8;
+        for (uint32_t d : {1u, 2u, 4u, 8u})
+            if (pow2_floor(c.width / d) <= ROLL_MAX_WINDOW && pow2_floor(c.height / d) <= ROLL_MAX_WINDOW) { G.d = d; break; }
+    }
+    if (c.width / G.d < ROLL_MIN_WINDOW || c.height / G.d < ROLL_MIN_WINDOW)
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "a frame of " + std::to_string(c.width) + "x" + std::to_string(c.height) + " has fewer than 32 decimated pixels on an axis (d = " + std::to_string(G.d) + ")");
+    G.nx = c.window_w ? c.window_w : std::min(ROLL_MAX_WINDOW, pow2_floor(c.width / G.d));
+    G.ny = c.window_h ? c.window_h : std::min(ROLL_MAX_WINDOW, pow2_floor(c.height / G.d));
+    if ((uint64_t)G.nx * G.d > c.width) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "window_w * d = " + std::to_string((uint64_t)G.nx * G.d) + " exceeds the frame's width " + std::to_string(c.width));
+    if ((uint64_t)G.ny * G.d > c.height) return fail(FFTUP_E_INVALID_ARG, std::string(who) + "window_h * d = " + std::to_string((uint64_t)G.ny * G.d) + " exceeds the frame's height " + std::to_string(c.height));
+    G.crop_x = (c.width - G.nx * G.d) / 2;
+    G.crop_y = (c.height - G.ny * G.d) / 2;
+    G.n = std::min(G.nx, G.ny);
+    G.ntheta = c.angles ? c.angles : G.n;
+    G.rho_max = (uint32_t)std::floor((double)G.band * (double)G.n);
+    G.rho_min = std::max(2u, G.rho_max / 4);
+    if (G.rho_max < G.rho_min)
+        return fail(FFTUP_E_INVALID_ARG, std::string(who) + "band " + std::to_string(G.band) + " leaves no radius: floor(band * " + std::to_string(G.n) + ") = " + std::to_string(G.rho_max) + " is below 2");
+    G.mb = G.ntheta / 4;
+    G.K = 2 * G.mb;
+    // cx <= n_x and cy <= n_y, the Nyquist bins of the padded transform (band <= 1).  The kernels keep columns -cx - 1 .. cx + 1, which
+    // for cx >= n_x - 1 (band = 1) are more than the 2 n_x bins of a row: the definition takes indices modulo the padded length, so
+    // column c simply holds bin (c - cx - 1) mod 2 n_x and up to three bins are stored twice, k_x and k_x - 2 n_x alike.  The column
+    // kernel pairs column k_x with column -k_x, which are bins k and -k modulo 2 n_x for every k_x up to cx + 1, wrapped or not, so
+    // the separation of A and B holds there too.  Rows need no wrap: cy + 1 <= n_y + 1 < 2 n_y.
+    G.cx = G.rho_max * (G.nx / G.n);
+    G.cy = G.rho_max * (G.ny / G.n);
+    return FFTUP_OK;
+}

@@ -142,3 +142,14 @@ struct RotateGeometry {
 };
 int rotate_geometry(const fftup_rotate_config& c, RotateGeometry& G);
 float const_via_percent_f(double v, bool half);
+
+// ---- fftup_roll_create: every rule and decision of a roll estimator (include/fftup.h, "roll estimates"), before any device access.
+// n = min(nx, ny); ntheta: angular samples over [0, pi); rho_min .. rho_max: the radii sampled, in bins of the transform padded to
+// 2 nx x 2 ny; mb: the angular frequencies 1 <= |m| <= mb that are correlated, K = 2 mb of them.  cx, cy: the largest |k_x| and k_y a
+// sample's lower-left bin can have (rho_max nx / n, rho_max ny / n): columns -cx - 1 .. cx + 1 and rows 0 .. cy + 1 are computed
+struct RollGeometry {
+    uint32_t W = 0, H = 0, precision = 0, nx = 0, ny = 0, d = 1, crop_x = 0, crop_y = 0, kappa = 32, max_batch = 16;
+    uint32_t n = 0, ntheta = 0, rho_min = 0, rho_max = 0, mb = 0, K = 0, cx = 0, cy = 0;
+    float band = 0.5f;
+};
+int roll_geometry(const fftup_roll_config& c, RollGeometry& G);
